@@ -20,6 +20,11 @@ called from C); torch.distributed only bootstraps (the 128-byte RCCL id, the bar
 witness is host-resident: every step uploads the rank's own trace and its 1/N slice of the claims. The independent-proof mode
 (one [ByteTable, U32Add] proof per GPU, host-resident witnesses, commitments all-gathered) is measured in the same run
 and reported as the secondary object `replicas`. Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...). Everything
+else - the profiled warm-up step and the roofline, the proof verification, stage times, the HBM-resident, pipelined,
+plain-upload and two-in-flight figures, the config-4 leg, the `replicas` leg and the CPU baseline - runs with --full.
+--dump-outputs DIR writes the proof bytes of the last timed step as DIR/proof.npy (float32, one element per byte).
 """
 import argparse
 import hashlib
@@ -61,7 +66,7 @@ def parse_args():
     ap.add_argument("--cpu-log-adds", type=int, default=20, help="size of the CPU baseline leg (same workload as the GPU by default)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-in-flight", action="store_true", help="N = 1: skip the secondary two-proofs-in-flight throughput figure")
-    ap.add_argument("--no-config4", action="store_true", help="N = 1: skip the secondary BASELINE-config-4 (BabyBear / Poseidon2) leg of the default run")
+    ap.add_argument("--no-config4", action="store_true", help="N = 1: skip the secondary BASELINE-config-4 (BabyBear / Poseidon2) leg of the --full run")
     ap.add_argument("--hbm-resident", action="store_true", help="N = 1: primary figure from a witness already resident in HBM "
                     "(round-1 definition) instead of the host-resident one")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL on ROCm; gloo only to "
@@ -79,7 +84,28 @@ def parse_args():
     ap.add_argument("--no-joint-leg", action="store_true", help="N > 1 with --replicas-primary: skip the joint proof")
     ap.add_argument("--primary-timeout", type=float, default=600.0, help="N > 1: seconds after which a leg that cannot finish (a "
                     "failed rank leaves the others in a collective) ends the job with a non-zero status")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement and check (roofline, verification, stage "
+                    "times, HBM-resident / pipelined / plain-upload / two-in-flight figures, config 4, replicas, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the proof bytes of the last timed step as DIR/proof.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, proof_bytes):
+    """The proof bytes a caller of the timed path receives, one float32 per byte (exact); a larger proof than the limit
+    allows is written as a fixed, seeded sample of its bytes, in order."""
+    a = np.frombuffer(proof_bytes, dtype=np.uint8).astype(np.float32)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(a.size, DUMP_LIMIT_BYTES // 4, replace=False))
+        a = a[keep]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "proof.npy"), a)
+    log("outputs written to %s: proof.npy (%d bytes of proof)" % (dirname, len(proof_bytes)))
 
 
 def log(*a):
@@ -153,6 +179,17 @@ def profile_first_step(ctx, step, rank, single_kernel_only=True):
         for n, s in ranked:
             if s["launches"]:
                 log("  %-16s launches %4d  total %8.3f ms  alg %.1f GB/s" % (n, s["launches"], s["ms"], s["alg_bytes"] / max(s["ms"], 1e-9) / 1e6))
+    return proof, dominant
+
+
+def warm_up(args, ctx, step, rank, single_kernel_only=True):
+    """the W warm-up steps (at least one); with --full the first one is profiled and names the dominant kernel class"""
+    if args.full:
+        proof, dominant = profile_first_step(ctx, step, rank, single_kernel_only)
+    else:
+        proof, dominant = step(), None
+    for _ in range(max(args.warmup, 1) - 1):
+        proof = step()
     return proof, dominant
 
 
@@ -269,13 +306,12 @@ def single_gpu(args, pkg, fe, ctx, torch):
         if torch is not None and torch.cuda.is_available():
             torch.cuda.synchronize()
 
-    proof, dominant = profile_first_step(ctx, step, 0)
-    for _ in range(max(args.warmup, 1) - 1):
-        proof = step()
+    proof, dominant = warm_up(args, ctx, step, 0)
     log("warm-up done (%d steps); timing %d steps" % (max(args.warmup, 1), args.steps))
-    # ---- timed region: exactly K steps, HIP events only around the dominant kernel class
-    ctx.set_profile([dominant])
-    ctx.reset_stats()
+    # ---- timed region: exactly K steps; with --full, HIP events only around the dominant kernel class
+    if dominant is not None:
+        ctx.set_profile([dominant])
+        ctx.reset_stats()
     sync()
     per = []
     t0 = time.perf_counter()
@@ -286,6 +322,17 @@ def single_gpu(args, pkg, fe, ctx, torch):
     sync()
     elapsed = time.perf_counter() - t0
     log("timed region done: %.3f ms per step (min %.3f, median %.3f, max %.3f)" % (1e3 * elapsed / args.steps, min(per), float(np.median(per)), max(per)))
+    result = base_line(args, 1, rows * args.steps / elapsed, 1e3 * elapsed / args.steps)
+    result["config"] = {
+        "workload": WORKLOAD % (args.log_adds, "proof", "witness resident in HBM" if args.hbm_resident else HOST_RESIDENT),
+        "rows_per_proof": rows,
+        "proof_bytes": len(proof.to_bytes()),
+        "parallelism": "single GPU",
+        "step_ms_min_median_max": [round(min(per), 3), round(float(np.median(per)), 3), round(max(per), 3)],  # box noise: the narrowing runs on shared host cores
+        "whole_path_alg_GBps": ALG_BYTES_PER_ROW * rows / (elapsed / args.steps) / 1e9,
+    }
+    if not args.full:
+        return result, proof.to_bytes()
     dom = ctx.kernel_stats()[dominant]
     ctx.set_profile([])
     stage = system.prove_multiple_claims(witness, want_times=True).stage_ms
@@ -351,16 +398,9 @@ def single_gpu(args, pkg, fe, ctx, torch):
     trace_bytes = int(sum(t.nbytes for t in traces))
     narrow = [int(t.nbytes // 8 * (1 if int(t.max(initial=0)) < 256 else 2 if int(t.max(initial=0)) < 65536 else 4 if int(t.max(initial=0)) < (1 << 32) else 8))
               if t.nbytes >= (4 << 20) else int(t.nbytes) for t in traces]
-    result = base_line(args, 1, rows * args.steps / elapsed, 1e3 * elapsed / args.steps)
-    result["config"] = {
-        "workload": WORKLOAD % (args.log_adds, "proof", "witness resident in HBM" if args.hbm_resident else HOST_RESIDENT),
-        "rows_per_proof": rows,
-        "proof_bytes": len(proof.to_bytes()),
+    result["config"].update({
         "verified": True,
-        "parallelism": "single GPU",
         "stage_ms": {k: round(v, 3) for k, v in stage.items()},
-        "step_ms_min_median_max": [round(min(per), 3), round(float(np.median(per)), 3), round(max(per), 3)],  # box noise: the narrowing runs on shared host cores
-        "whole_path_alg_GBps": ALG_BYTES_PER_ROW * rows / (elapsed / args.steps) / 1e9,
         "hbm_resident_ms": hbm_ms,
         "pipelined_ms_per_proof": pipe_ms,
         "two_in_flight": in_flight,
@@ -372,11 +412,11 @@ def single_gpu(args, pkg, fe, ctx, torch):
             "bytes_over_pcie_per_proof": int(sum(narrow) + packed[0].nbytes + packed[1].nbytes),
             "plain_upload_ms_per_proof": plain_ms,
         },
-    }
+    })
     result["roofline"] = roofline_of(dominant, dom, full_size=(args.log_adds == 20))  # (the committed counter pass is of 2^20 additions)
     if not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(fe, system.blob, args.cpu_log_adds)
-    return result
+    return result, proof.to_bytes()
 
 
 def two_in_flight(pkg, fe, system, witness, traces, packed, want, rows, k):
@@ -444,9 +484,7 @@ def babybear(args, pkg, fe, ctx, torch):
     def step():
         return system.prove_multiple_claims(witness)
 
-    proof, dominant = profile_first_step(ctx, step, 0, single_kernel_only=False)
-    for _ in range(max(args.warmup, 1) - 1):
-        proof = step()
+    proof, dominant = warm_up(args, ctx, step, 0, single_kernel_only=False)
     # ---- timed region: exactly K steps, NO HIP events (this configuration's dominant class is ~150 short launches per proof:
     # events around each of them cost about a millisecond per proof, which is not the prover's time)
     ctx.set_profile([])
@@ -460,6 +498,20 @@ def babybear(args, pkg, fe, ctx, torch):
     ctx.sync()
     elapsed = time.perf_counter() - t0
     log("timed region done: %.3f ms per step (min %.3f, median %.3f, max %.3f)" % (1e3 * elapsed / args.steps, min(per), float(np.median(per)), max(per)))
+    result = base_line(args, 1, rows * args.steps / elapsed, 1e3 * elapsed / args.steps)
+    result["dtype"] = "u32"
+    result["config"] = {
+        "workload": "BASELINE config 4: MulAir (a * b = c with a self-cancelling lookup pair), 2^%d rows, BabyBear / degree-4 extension / "
+                    "Poseidon2-16 sponge and compression / DuplexChallenger (src/test_circuits/baby_bear_config.rs), log_blowup 1, 64 queries; "
+                    "%s, proof bytes returned to host" % (args.log_adds, "witness resident in HBM" if args.hbm_resident else
+                                                           "witness (canonical u32 words) in pinned host memory at step start, uploaded inside the step"),
+        "rows_per_proof": rows,
+        "proof_bytes": len(proof.to_bytes()),
+        "parallelism": "single GPU",
+        "step_ms_min_median_max": [round(min(per), 3), round(float(np.median(per)), 3), round(max(per), 3)],
+    }
+    if not args.full:
+        return result, proof.to_bytes()
     # ---- the dominant class's launch times: a separate pass with events around that class only, outside the timed region
     prof_steps = max(2, min(args.steps, 5))
     ctx.set_profile([dominant])
@@ -486,21 +538,11 @@ def babybear(args, pkg, fe, ctx, torch):
         ctx.sync()
         hbm_ms = 1e3 * (time.perf_counter() - t1) / k
         del dw
-    result = base_line(args, 1, rows * args.steps / elapsed, 1e3 * elapsed / args.steps)
-    result["dtype"] = "u32"
-    result["config"] = {
-        "workload": "BASELINE config 4: MulAir (a * b = c with a self-cancelling lookup pair), 2^%d rows, BabyBear / degree-4 extension / "
-                    "Poseidon2-16 sponge and compression / DuplexChallenger (src/test_circuits/baby_bear_config.rs), log_blowup 1, 64 queries; "
-                    "%s, proof bytes returned to host" % (args.log_adds, "witness resident in HBM" if args.hbm_resident else
-                                                           "witness (canonical u32 words) in pinned host memory at step start, uploaded inside the step"),
-        "rows_per_proof": rows,
-        "proof_bytes": len(proof.to_bytes()),
+    result["config"].update({
         "verified": True,
-        "parallelism": "single GPU",
         "stage_ms": {k: round(v, 3) for k, v in stage.items()},
-        "step_ms_min_median_max": [round(min(per), 3), round(float(np.median(per)), 3), round(max(per), 3)],
         "hbm_resident_ms": hbm_ms,
-    }
+    })
     rl = roofline_of(dominant, dom, full_size=False)
     rl["traffic"], rl["traffic_source"] = None, "not collected for this configuration"
     rl["timed_how"] = ("HIP events around every launch of this class in a SEPARATE pass of %d steps after the timed region (%.3f ms per step "
@@ -515,7 +557,7 @@ def babybear(args, pkg, fe, ctx, torch):
     result["roofline"] = rl
     if not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_babybear(system.blob, trace, packed, proof.to_bytes(), rows)
-    return result
+    return result, proof.to_bytes()
 
 
 def cpu_baseline_babybear(blob, trace, packed, gpu_proof, rows):
@@ -547,7 +589,7 @@ def cpu_baseline_babybear(blob, trace, packed, gpu_proof, rows):
 
 # ------------------------------------------------------------------------------------------------ N > 1
 def timed_steps(args, ctx, torch, dist, step, sync_extra, dev):
-    """W warm-up steps (the first one profiled), then exactly K steps between barrier + synchronize; max over ranks"""
+    """W warm-up steps (with --full the first one profiled), then exactly K steps between barrier + synchronize; max over ranks"""
     rank = dist.get_rank()
 
     def sync_all():
@@ -559,11 +601,10 @@ def timed_steps(args, ctx, torch, dist, step, sync_extra, dev):
         if torch.cuda.is_available():
             torch.cuda.synchronize()
 
-    proof, dominant = profile_first_step(ctx, step, rank)
-    for _ in range(max(args.warmup, 1) - 1):
-        proof = step()
-    ctx.set_profile([dominant])
-    ctx.reset_stats()
+    proof, dominant = warm_up(args, ctx, step, rank)
+    if dominant is not None:
+        ctx.set_profile([dominant])
+        ctx.reset_stats()
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -572,8 +613,10 @@ def timed_steps(args, ctx, torch, dist, step, sync_extra, dev):
     elapsed = time.perf_counter() - t0
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-    dom = ctx.kernel_stats()[dominant]
-    ctx.set_profile([])
+    dom = None
+    if dominant is not None:
+        dom = ctx.kernel_stats()[dominant]
+        ctx.set_profile([])
     return proof, float(tmax.item()), dominant, dom
 
 
@@ -615,7 +658,7 @@ def replicas_leg(args, pkg, fe, ctx, torch, dist, mgpu, rank, local_rank, traces
                 "every proof all-gathered (RCCL) and digested on rank 0" % args.log_adds,
         "value": rows * world * args.steps / elapsed, "unit": "rows/s", "ms_per_step": 1e3 * elapsed / args.steps,
         "rows_per_proof": rows, "proofs_per_step": world, "proof_bytes": len(proof.to_bytes()),
-    }, dominant, dom, rows
+    }, dominant, dom, rows, proof.to_bytes()
 
 
 def joint_preflight(args, pkg, fe, ctx, torch, dist, sharded, system, comm, owners, rank, world, dev, wd):
@@ -713,7 +756,7 @@ def joint_leg(args, pkg, fe, ctx, torch, dist, rank, local_rank, traces, claims,
     comm.bytes_moved = 0
     proof, elapsed, dominant, dom = timed_steps(args, ctx, torch, dist, step, lambda: None, dev)
     moved = comm.bytes_moved // (args.steps + max(args.warmup, 1))
-    stage = system.prove_sharded(witness, comm, owners, want_times=True).stage_ms
+    stage = system.prove_sharded(witness, comm, owners, want_times=True).stage_ms if args.full else None
     sha = hashlib.sha256(proof.to_bytes()).hexdigest()
     # untimed: the joint proof must be accepted by the library's verifier (System::verify_multiple_claims on the bytes); a
     # wrong exchange on first contact with several GPUs must not pass as a measurement
@@ -727,12 +770,12 @@ def joint_leg(args, pkg, fe, ctx, torch, dist, rank, local_rank, traces, claims,
                 "totals / opened values / reduced openings all-gathered" % (world, world),
         "value": rows * args.steps / elapsed, "unit": "rows/s", "ms_per_step": 1e3 * elapsed / args.steps,
         "rows_per_proof": rows, "proof_bytes": len(proof.to_bytes()), "proof_sha256": sha, "transport": transport,
-        "bytes_exchanged_per_rank_per_proof": moved, "stage_ms": {k: round(v, 3) for k, v in stage.items()},
+        "bytes_exchanged_per_rank_per_proof": moved, "stage_ms": stage and {k: round(v, 3) for k, v in stage.items()},
         "verified": verdict == 0, "preflight": preflight,
     }
     if verdict != 0:
         info["error"] = "the joint proof is REJECTED by the verifier (code %d): the figures of this leg are void" % verdict
-    return info, dominant, dom, rows
+    return info, dominant, dom, rows, proof.to_bytes()
 
 
 def multi_gpu(args, pkg, fe, ctx, torch, dist, rank, local_rank, n_gpus):
@@ -791,12 +834,12 @@ def multi_gpu(args, pkg, fe, ctx, torch, dist, rank, local_rank, n_gpus):
     if joint_primary:
         failed = run_joint()
         if failed is not None:
-            return failed
+            return failed, None
     else:
         run_replicas()
     wd.finish()
     prim = done["joint"] if joint_primary else done["replicas"]
-    info, dominant, dom, rows = prim
+    info, dominant, dom, rows, proof_bytes = prim
     result = base_line(args, n_gpus, info["value"], info["ms_per_step"])
     result["config"] = {
         "workload": WORKLOAD % (args.log_adds, "rank" if joint_primary else "proof",
@@ -820,11 +863,12 @@ def multi_gpu(args, pkg, fe, ctx, torch, dist, rank, local_rank, n_gpus):
         result["config"]["verified"] = info["verified"]
         if "error" in info:
             result["error"] = info["error"]
-    result["roofline"] = roofline_of(dominant, dom, full_size=False)
+    if dom is not None:
+        result["roofline"] = roofline_of(dominant, dom, full_size=False)
     if joint_primary:
         result["config"]["preflight"] = info.get("preflight")
     # ---- the secondary leg, behind a watchdog of its own that prints the primary line (status 0) if the leg cannot finish
-    want_secondary = (joint_primary and not args.no_replicas_leg) or (not joint_primary and not args.no_joint_leg)
+    want_secondary = args.full and ((joint_primary and not args.no_replicas_leg) or (not joint_primary and not args.no_joint_leg))
     if want_secondary and not result.get("error"):
         wd2 = Watchdog(rank, "the secondary leg of the multi-GPU bench", min(args.primary_timeout, 240.0), lambda: result, ctx, soft=True)
         try:
@@ -844,14 +888,14 @@ def multi_gpu(args, pkg, fe, ctx, torch, dist, rank, local_rank, n_gpus):
                 print(json.dumps(result), flush=True)
             os._exit(0)  # (no closing barrier: a rank that failed inside a collective would never join it)
         wd2.finish()
-    if not args.no_cpu_baseline and rank == 0:
+    if args.full and not args.no_cpu_baseline and rank == 0:
         # the same CPU leg as at N = 1 (one [ByteTable, U32Add] proof at 2^cpu-log-adds additions on this box's host cores): rows/s of
         # the restatement does not depend on how many adders the system holds. The other ranks wait at the closing barrier.
         one = pkg.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs())
         result["cpu_baseline"] = cpu_baseline(fe, one.blob, args.cpu_log_adds)
         result["cpu_baseline"]["sample"] += "; measured on rank 0's host cores while the other ranks idle"
         del one
-    return result
+    return result, proof_bytes
 
 
 def fail_line(args, why, code=2):
@@ -934,12 +978,11 @@ def local_multi_gpu(args):
     wd = Watchdog(0, "the multi-GPU bench (thread ranks)", args.primary_timeout, partial, _Progress())
 
     def timed(ctx, step, rank):
-        """W warm-up steps (the first one profiled), then exactly K steps between barrier + device synchronisation"""
-        proof, dominant = profile_first_step(ctx, step, rank)
-        for _ in range(max(args.warmup, 1) - 1):
-            proof = step()
-        ctx.set_profile([dominant])
-        ctx.reset_stats()
+        """W warm-up steps (with --full the first one profiled), then exactly K steps between barrier + device synchronisation"""
+        proof, dominant = warm_up(args, ctx, step, rank)
+        if dominant is not None:
+            ctx.set_profile([dominant])
+            ctx.reset_stats()
         ctx.sync()
         barrier.wait()
         t0 = time.perf_counter()
@@ -951,8 +994,10 @@ def local_multi_gpu(args):
         ctx.sync()
         barrier.wait()  # every rank has synchronised its device: the slowest rank closes the region
         elapsed = time.perf_counter() - t0
-        dom = ctx.kernel_stats()[dominant]
-        ctx.set_profile([])
+        dom = None
+        if dominant is not None:
+            dom = ctx.kernel_stats()[dominant]
+            ctx.set_profile([])
         return proof, elapsed, dominant, dom, per
 
     def rank_body(rank, group):
@@ -984,16 +1029,16 @@ def local_multi_gpu(args):
                 wd.leg = "joint proof, warm-up and timed steps"
             proof, elapsed, dominant, dom, per = timed(ctx, step, rank)
             moved = (comm.bytes_moved - moved0) // (args.steps + max(args.warmup, 1))
-            stage = system.prove_sharded(witness, comm, owners, want_times=True).stage_ms
+            stage = system.prove_sharded(witness, comm, owners, want_times=True).stage_ms if args.full else None
             data = proof.to_bytes()
             res["joint"] = {"elapsed": elapsed, "per_step_ms": per, "dominant": dominant, "dom": dom, "moved": moved, "stage": stage,
-                            "sha": hashlib.sha256(data).hexdigest(), "bytes": len(data),
+                            "sha": hashlib.sha256(data).hexdigest(), "bytes": len(data), "proof": data,
                             "verdict": system.verify_multiple_claims(packed, data) if rank == 0 else 0}
             del witness
         finally:
             comm.close()
         # ---- secondary leg, behind the primary one: one independent [ByteTable, U32Add] proof per rank per step
-        if not args.no_replicas_leg and "joint" in res:
+        if args.full and not args.no_replicas_leg and "joint" in res:
             if rank == 0:
                 wd.leg = "replicas (one independent proof per rank)"
             one = pkg.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs())
@@ -1015,7 +1060,7 @@ def local_multi_gpu(args):
         line = partial()
         line["error"] = "joint proof by thread ranks failed (%s): %s" % (where, e)
         log(line["error"])
-        return line
+        return line, None
     finally:
         group.close()
     wd.finish()
@@ -1027,7 +1072,7 @@ def local_multi_gpu(args):
                  "what": "joint proof of [ByteTable, U32Add x %d] at 2^%d additions per rank == System::prove_multiple_claims of the full system on "
                          "device %d, byte for byte, from host- and device-resident witnesses; same bytes on every rank; verifier accepts" % (N, k, devices[0])}
     replicas = None
-    if not args.no_replicas_leg and all("replicas" in r for r in results):
+    if args.full and not args.no_replicas_leg and all("replicas" in r for r in results):
         el = max(r["replicas"][0] for r in results)
         replicas = {"what": "one independent [ByteTable, U32Add @ 2^%d] proof per rank per step (thread ranks, host-resident witnesses)" % args.log_adds,
                     "value": results[0]["replicas"][2] * N * args.steps / el, "unit": "rows/s", "ms_per_step": 1e3 * el / args.steps,
@@ -1038,7 +1083,7 @@ def local_multi_gpu(args):
         line["error"] = "joint proof pre-flight failed: the joint proof differs from the single-GPU proof of the same system (or between ranks)"
         line["preflight"] = preflight
         line["config"] = {"ranks": ranks_info}
-        return line
+        return line, None
     joint = [r["joint"] for r in results]
     elapsed = max(j["elapsed"] for j in joint)
     same = len({j["sha"] for j in joint}) == 1
@@ -1052,15 +1097,16 @@ def local_multi_gpu(args):
         "parallelism": "one joint proof over %d %s (ms_prove_sharded, transport local)" % (N, "thread ranks SHARING %d device(s): rehearsal" % len(set(devices)) if shared else "GPUs"),
         "ranks": ranks_info,
         "whole_path_alg_GBps": ALG_BYTES_PER_ROW * rows / (elapsed / args.steps) / 1e9,
-        "stage_ms": {k_: round(v, 3) for k_, v in j0["stage"].items()},
+        "stage_ms": j0["stage"] and {k_: round(v, 3) for k_, v in j0["stage"].items()},
         "step_ms_min_median_max": [round(float(np.min(per)), 3), round(float(np.median(per)), 3), round(float(np.max(per)), 3)],
         "bytes_exchanged_per_rank_per_proof": j0["moved"], "proof_sha256": j0["sha"], "verified": j0["verdict"] == 0 and same,
         "preflight": preflight,
     }
     if j0["verdict"] != 0 or not same:
         result["error"] = ("the joint proof is REJECTED by the verifier (code %d)" % j0["verdict"]) if j0["verdict"] else "the ranks hold different proof bytes"
-    result["roofline"] = roofline_of(j0["dominant"], j0["dom"], full_size=False)
-    if not args.no_cpu_baseline:
+    if j0["dom"] is not None:
+        result["roofline"] = roofline_of(j0["dominant"], j0["dom"], full_size=False)
+    if args.full and not args.no_cpu_baseline:
         ctx = pkg.Context(devices[0])
         one = pkg.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs())
         result["cpu_baseline"] = cpu_baseline(fe, one.blob, args.cpu_log_adds)
@@ -1068,7 +1114,7 @@ def local_multi_gpu(args):
         del one, ctx
     if replicas is not None:
         result["replicas"] = replicas
-    return result
+    return result, j0["proof"]
 
 
 def main():
@@ -1090,7 +1136,9 @@ def main():
         if args.config == "babybear":
             fail_line(args, "--config babybear is a single-GPU measurement")
         # no launcher environment: ONE process drives the N devices itself, as the reference's prover does
-        result = local_multi_gpu(args)
+        result, proof_bytes = local_multi_gpu(args)
+        if args.dump_outputs and proof_bytes is not None:
+            dump_outputs(args.dump_outputs, proof_bytes)
         print(json.dumps(result), flush=True)
         if result.get("error"):
             sys.exit(4)
@@ -1103,9 +1151,11 @@ def main():
 
     torch = None
     try:
-        import torch as _torch
+        # a plain one-GPU run synchronises with the library's own stream (ctx.sync) and leaves torch's start-up out
+        if n_gpus > 1 or force_dist or args.full:
+            import torch as _torch
 
-        torch = _torch
+            torch = _torch
     except Exception as e:  # torch is plumbing only (barrier / synchronize / bootstrap); never needed for the proof itself
         if n_gpus > 1 or force_dist:
             raise
@@ -1130,25 +1180,25 @@ def main():
     if args.config == "babybear":
         if dist is not None:
             raise SystemExit("--config babybear is a single-GPU measurement")
-        result = babybear(args, pkg, fe, ctx, torch)
+        result, proof_bytes = babybear(args, pkg, fe, ctx, torch)
     elif dist is None:
-        result = single_gpu(args, pkg, fe, ctx, torch)
-        if not args.no_config4 and not args.hbm_resident and args.log_adds == 20:
+        result, proof_bytes = single_gpu(args, pkg, fe, ctx, torch)
+        if args.full and not args.no_config4 and not args.hbm_resident and args.log_adds == 20:
             # BASELINE config 4 (the reference's second StarkGenericConfig) as a secondary object of the same line, so that the
-            # run that records config 2 also records it; its full line (roofline, CPU baseline) is `--config babybear`
+            # run that records config 2 also records it; its full line (roofline, CPU baseline) is `--config babybear --full`
             try:
                 import copy
 
                 a4 = copy.copy(args)
                 a4.steps, a4.warmup, a4.no_cpu_baseline = max(3, min(args.steps, 10)), 2, True
-                r4 = babybear(a4, pkg, fe, ctx, torch)
+                r4, _ = babybear(a4, pkg, fe, ctx, torch)
                 result["config4_babybear"] = {
                     "what": "BASELINE config 4, secondary leg of this run: " + r4["config"]["workload"],
                     "value": r4["value"], "unit": r4["unit"], "ms_per_step": r4["ms_per_step"], "steps": a4.steps,
                     "hbm_resident_ms": r4["config"]["hbm_resident_ms"], "stage_ms": r4["config"]["stage_ms"],
                     "proof_bytes": r4["config"]["proof_bytes"], "verified": r4["config"]["verified"],
                     "step_ms_min_median_max": r4["config"]["step_ms_min_median_max"],
-                    "note": "timed without HIP events; the dominant kernel class (%s) is timed in a separate pass (`--config babybear` "
+                    "note": "timed without HIP events; the dominant kernel class (%s) is timed in a separate pass (`--config babybear --full` "
                             "prints the full line with roofline and CPU baseline)" % r4["roofline"]["kernel"]}
                 log("config 4 (BabyBear / Poseidon2) secondary leg: %.3f ms per step, %.3f ms HBM-resident" % (
                     r4["ms_per_step"], r4["config"]["hbm_resident_ms"] or float("nan")))
@@ -1156,10 +1206,12 @@ def main():
                 log("config 4 secondary leg failed: %r" % (e,))
                 result["config4_babybear"] = {"error": "config 4 secondary leg failed: %r" % (e,)}
     else:
-        result = multi_gpu(args, pkg, fe, ctx, torch, dist, rank, local_rank, n_gpus)
+        result, proof_bytes = multi_gpu(args, pkg, fe, ctx, torch, dist, rank, local_rank, n_gpus)
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs and proof_bytes is not None:
+            dump_outputs(args.dump_outputs, proof_bytes)
         print(json.dumps(result), flush=True)
     if result.get("error"):
         sys.exit(4)  # a rejected proof is a failed run, whatever was timed

@@ -1,12 +1,14 @@
 """bench.py as the driver runs it. CPU: a command that names more GPUs than there are must FAIL (non-zero status, a JSON line
 with the reason), never measure fewer; a launcher world that disagrees with --gpus likewise. GPU: the N > 1 code path of
 `python3 bench.py --gpus N` - N thread ranks of one process on the library's in-process transport, the form the driver's
-launcher-less call takes - runs with 2 ranks rehearsed on the one device and its line carries what the judge asks for."""
+launcher-less call takes - runs with 2 ranks rehearsed on the one device and its line carries what the judge asks for. A plain
+N = 1 run reports the timed steps only and dumps the last step's proof; --full adds the secondary figures."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,6 +37,11 @@ def test_launcher_world_must_agree_with_gpus():
     assert r.returncode != 0 and "must agree" in r.stderr and line["value"] is None
 
 
+def test_steps_must_be_at_least_one():
+    r, _ = _bench("--steps", "0")
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
 def test_process_per_gpu_transports_need_a_launcher():
     r, line = _bench("--gpus", "2", "--transport", "rccl")
     assert r.returncode != 0 and "torch.distributed.run" in r.stderr and line["error"]
@@ -43,7 +50,7 @@ def test_process_per_gpu_transports_need_a_launcher():
 @pytest.mark.gpu
 def test_bench_thread_ranks_two_ranks_on_one_device():
     """the launcher-less N > 1 path with 2 thread ranks sharing the test box's one device (--share-devices: a labelled rehearsal)"""
-    r, line = _bench("--gpus", "2", "--share-devices", "--log-adds", "12", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    r, line = _bench("--gpus", "2", "--share-devices", "--log-adds", "12", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0 and "error" not in line
     cfg = line["config"]
@@ -62,3 +69,29 @@ def test_bench_refuses_two_gpus_on_a_one_gpu_box(pkg):
         pytest.skip("this box shows %d devices" % pkg.device_count())
     r, line = _bench("--gpus", "2", "--steps", "1", "--warmup", "1")
     assert r.returncode != 0 and "needs 2 HIP devices, this process sees 1" in r.stderr and line["value"] is None
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_proof(pkg, ctx, oracle, fe, tmp_path):
+    """a plain run times exactly --steps steps, carries no secondary figure, and --dump-outputs writes the proof bytes of the
+    last timed step: the oracle's proof of the same witness, byte for byte"""
+    r, line = _bench("--gpus", "1", "--log-adds", "12", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert "timing 3 steps" in r.stderr and line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["metric"] == "prove_trace_rows_per_sec" and line["unit"] == "rows/s" and line["dtype"] == "u64" and line["higher_is_better"] is True
+    assert not {"roofline", "cpu_baseline", "config4_babybear"} & set(line) and "hbm_resident_ms" not in line["config"]
+    got = np.load(str(tmp_path / "proof.npy"))
+    assert got.dtype == np.float32 and got.size == line["config"]["proof_bytes"]
+    traces, claims = fe.u32_add_bench_witness(1 << 12)
+    system = pkg.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs())
+    assert got.astype(np.uint8).tobytes() == oracle.System(system.blob).prove(traces, fe.pack_claims(claims))
+
+
+@pytest.mark.gpu
+def test_bench_full_run_keeps_the_secondary_figures():
+    r, line = _bench("--gpus", "1", "--log-adds", "12", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full")
+    assert r.returncode == 0, r.stderr[-3000:]
+    cfg = line["config"]
+    assert cfg["verified"] is True and cfg["stage_ms"]["total"] > 0 and cfg["hbm_resident_ms"] > 0 and cfg["pipelined_ms_per_proof"] > 0
+    assert cfg["upload"]["plain_upload_ms_per_proof"] > 0 and cfg["two_in_flight"]["ms_per_proof"] > 0
+    assert line["roofline"]["bound"] == "hbm" and line["roofline"]["achieved"] > 0
