@@ -121,7 +121,7 @@ int32_t ms_witness_create(ms_system* sys, const uint64_t* const* traces, const u
  * sent as 64-bit words: every ms_prove narrows it on a pool of host threads (16 by default), checking the range again, uploads the narrowed chunks as they complete and widens them on the device - at the
  * bench size 15 MB instead of 117 MB cross PCIe, in 0.5 ms instead of 2.1. A value that no longer fits sends that proof
  * down the plain path. Environment: MSAMD_NO_PACK=1 (read here) never narrows; MSAMD_PACK_THREADS=n (0: off),
- * MSAMD_PACK_MIN_BYTES, MSAMD_PACK_CHUNKS, MSAMD_PACK_AFFINITY=1 (workers confined to the NUMA node of the trace) tune it. */
+ * MSAMD_PACK_MIN_BYTES, MSAMD_PACK_CHUNKS tune it. */
 int32_t ms_witness_create_host(ms_system* sys, const uint64_t* const* traces, const uint64_t* heights, size_t n_claims,
                                const uint64_t* claim_offsets, const uint64_t* claim_data, int32_t* pinned /* nullable */,
                                ms_witness** out);

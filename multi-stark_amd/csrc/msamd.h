@@ -63,9 +63,9 @@ struct Ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t copy_stream = nullptr;  // bulk uploads of a host-resident witness, running beside the kernels of `stream`
-  hipStream_t claims_stream = nullptr;  // the claims of a host-resident witness: DMA copies beside the trace's pulling kernels
-  std::vector<hipEvent_t> group_events;  // one per row group of a narrow upload in flight, created on demand (group_event)
-  hipEvent_t group_event(size_t i);
+  // (no upload is queued here any more: the claims travel on the copy stream. The stream is still created, synchronised and
+  // waited on as before, so that the other streams keep their hardware queues)
+  hipStream_t claims_stream = nullptr;
   // Side stream for the short circuits of a system (prover.hip): between side_fork() and side_join() the launches queued
   // inside a SideScope go to `side_stream` (the scope swaps `stream`) and run beside the long kernels of the main stream
   // instead of in front of them. Blocks allocated inside a scope come from a pool of their own (`pool_free_side`), and a
@@ -261,22 +261,17 @@ struct NttSrc {
   const u64* scale = nullptr;    // per destination column group: scale + (c % src_div) * 2^logn
 };
 void ntt_dif(Ctx& ctx, u64* data, unsigned logn, size_t ncols, bool inverse, const NttSrc* from = nullptr, u64 out_mul = 1);
-void ntt_dit(Ctx& ctx, u64* data, unsigned logn, size_t ncols, bool inverse, u64 out_mul = 1, bool first_pass_done = false);
-// the first (4096-row tile) pass of ntt_dit on one of eight row groups; ntt_dit(.., first_pass_done = true) finishes (ntt.hip)
-void ntt_dit_first_pass_part(Ctx& ctx, u64* data, unsigned logn, size_t ncols, bool inverse, unsigned part_rev);
-void transpose_in_rows_part(Ctx& ctx, const u64* rowmajor, u64* colmajor, size_t h, size_t w, unsigned part);
-void pull_widen_runs(const uint8_t* host_packed, unsigned bytes, size_t count, u64* out, size_t run_words, size_t run_stride, hipStream_t stream);
+void ntt_dit(Ctx& ctx, u64* data, unsigned logn, size_t ncols, bool inverse, u64 out_mul = 1);
 // row-major host layout (h x w) on device -> column-major, optionally with rows bit-reversed
 void transpose_in(Ctx& ctx, const u64* rowmajor, u64* colmajor, size_t h, size_t w, bool bitrev_rows);
 void transpose_out(Ctx& ctx, const u64* colmajor, u64* rowmajor, size_t h, size_t w, bool bitrev_rows);
-// out[i] = the i-th little-endian `bytes`-byte value of `packed` (bytes = 1, 2, 4), on `stream`
-void widen_words(const uint8_t* packed, unsigned bytes, size_t count, u64* out, hipStream_t stream);
-// the same from PINNED HOST memory, read by the kernel itself (no staging copy): host_packed 16-byte aligned
+// out[i] = the i-th little-endian `bytes`-byte value of `host_packed` (bytes = 1, 2, 4), on `stream`, read from PINNED HOST
+// memory by the kernel itself (no staging copy): host_packed 16-byte aligned
 void pull_widen_words(const uint8_t* host_packed, unsigned bytes, size_t count, u64* out, hipStream_t stream);
 // coefficients (unscaled inverse DFT output, natural order, column-major n x w) -> bit-reversed coset LDE (Bn x w)
 void lde_from_coeffs(Ctx& ctx, const u64* coef, u64* lde, unsigned logn, unsigned log_blowup, size_t w);
 // evaluations in bit-reversed row order (column-major n x w, destroyed) -> bit-reversed coset LDE (Bn x w)
-void coset_lde(Ctx& ctx, u64* evals_bitrev, u64* lde, unsigned logn, unsigned log_blowup, size_t w, bool first_pass_done = false);
+void coset_lde(Ctx& ctx, u64* evals_bitrev, u64* lde, unsigned logn, unsigned log_blowup, size_t w);
 // src/prover.rs:631-717 fused: quotient values in storage (bit-reversed) order, nq x D column-major (destroyed)
 // -> committed quotient LDE (B n x qD)
 void quotient_lde(Ctx& ctx, u64* qvals_bitrev, u64* lde, unsigned logn, unsigned logq, unsigned log_blowup, size_t D);
@@ -489,46 +484,13 @@ struct DeepPoints {
   uint32_t shift[2];    // 0, or: z_q = z' * w^shift for the point z' whose denominators den[q] holds (w = the domain's generator);
                         // the kernel then reads den[q] through open.hip::rev_dec, and K / the coefficients carry the factor w^-shift
 };
-// ---- the opened values' transcript step on the device (open.hip::open_alpha_k; src/prover.rs:540-580 -> p3 TwoAdicFriPcs::open):
-// finish the barycentric sums, absorb every opened value into the transcript (BLAKE3 of state || values), sample the FRI batching
-// challenge alpha and fill what the reduced openings need from it - alpha's powers, every matrix's coefficients, every height's
-// constants K - so that nothing between the barycentric sums and the end of FRI waits for the host. The host replays the step
-// from the raw sums afterwards (it is the authority on the challenge; the values are the kernels' output either way).
-struct OpenEntry {      // one (matrix, point) of the opening, in the transcript's observe order (round -> matrix -> point)
-  uint32_t sum_off;     // the matrix's raw sums start here in the sums array (value of column c, point p at sum_off + c * np + p)
-  uint32_t out_off;     // where this entry's w finished values go in the opened array (= observe order)
-  uint32_t w, np, p;    // columns; points of the matrix; which of them this entry is
-  uint32_t log_h;       // log2 of the trace height (the barycentric domain: the coset of 2^log_h points)
-  uint32_t point_id;    // the point's index in the device point array (zeta, zeta * g ...)
-  uint32_t mat;         // index of the matrix's DeepMat in the blob; ~0 = no reduced opening for it
-  uint32_t exp;         // its coefficient is alpha^exp ...
-  uint32_t slot;        // ... and coeff * sum_c alpha^c y_c is added to K[slot]
-  uint64_t s_pow, dinv; // 7^(2^log_h) and 1 / (2^log_h * s_pow): the finishing factor is (z^(2^log_h) - s_pow) * dinv
-  uint64_t cmul;        // the coefficient's extra factor (1, or g^-1 for a point read through another one's denominators)
-};
-struct OpenAlphaArgs {
-  const OpenEntry* entries;
-  uint32_t n_entries, n_vals, gw, n_slots;
-  const E2* sums;       // raw barycentric sums
-  const E2* points;     // device opening points
-  const uint32_t* state_in;  // 8 words: the challenger's input buffer (the digest its last sample left)
-  E2* opened;           // n_vals finished values in observe order
-  E2* apow;             // gw + 1 powers of alpha
-  struct DeepMat* mats; // the DeepMat blob: coeff / coeff7 are filled here
-  E2* K;                // n_slots constants
-  uint32_t* state_out;  // 8 words: the input buffer after the sample (where FRI's transcript goes on)
-  E2* alpha_out;
-  Digest* cv_scratch;   // one chaining value per 1024 bytes of transcript
-};
-void open_alpha(Ctx& ctx, const OpenAlphaArgs& a);
 // ro[i] = sum over matrices/points of coeff * (red_z - sum_c alpha^c m[i][c]) / (z - x_i)
 // alpha_pows_host (optional): the same powers on the host; short lists then travel inside the kernel's argument block
 void deep_reduce(Ctx& ctx, const std::vector<DeepMat>& mats, const DeepPoints& pts, size_t height, const E2* alpha_pows_dev, E2* ro,
                  const E2* alpha_pows_host = nullptr, Digest* fri_leaves = nullptr /* height / 2 leaf digests of FRI's first round */,
                  const DeepMat* mats_dev = nullptr /* the list already in device memory */,
                  size_t row0 = 0, size_t full_height = 0 /* rows [row0, row0 + height) of a domain of full_height rows (0 = height): pts.den
-                                                            are indexed by the FULL domain's row */,
-                 const E2* K_dev = nullptr /* the points' constants K in device memory (open_alpha_k) instead of pts.K */);
+                                                            are indexed by the FULL domain's row */);
 // FRI: leaves of pairs -> digests handled by merkle_build on a 4-column view; fold:
 // row0 / rows_total: `cur`, `roll_in`, `out` are the slice [row0, row0 + rows) of a folded layer of rows_total rows (0 = whole layer)
 void fri_fold(Ctx& ctx, const E2* cur, size_t rows, E2 beta, const E2* roll_in /*nullable*/, E2* out, size_t row0 = 0, size_t rows_total = 0);

@@ -9,9 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include <sched.h>
 #include <sys/resource.h>
-#include <sys/syscall.h>
 #include <unistd.h>
 
 #include <atomic>
@@ -187,17 +185,15 @@ void commit_matrices(Ctx& ctx, std::vector<DMat>&& ldes, unsigned cap_height, Pc
 }
 
 // host row-major evaluations -> device bit-reversed coset LDE
-// (`early`: the matrix already transposed and through the first pass of the inverse transform - HostUpload's row groups; taken over)
-static DMat lde_of_host_matrix(Ctx& ctx, const u64* rowmajor_dev, size_t h, size_t w, unsigned lb, DBuf<u64>* early = nullptr) {
+static DMat lde_of_host_matrix(Ctx& ctx, const u64* rowmajor_dev, size_t h, size_t w, unsigned lb) {
   unsigned logn = log2_strict(h);
-  const bool first_pass_done = early && early->p;
-  DBuf<u64> ev = first_pass_done ? std::move(*early) : DBuf<u64>(ctx, h * w);
-  if (!first_pass_done) transpose_in(ctx, rowmajor_dev, ev.p, h, w, true);
+  DBuf<u64> ev(ctx, h * w);
+  transpose_in(ctx, rowmajor_dev, ev.p, h, w, true);
   DMat lde;
   lde.h = h << lb;
   lde.w = w;
   lde.buf = DBuf<u64>(ctx, lde.h * w);
-  coset_lde(ctx, ev.p, lde.d(), logn, lb, w, first_pass_done);
+  coset_lde(ctx, ev.p, lde.d(), logn, lb, w);
   return lde;
 }
 
@@ -540,50 +536,12 @@ namespace {
 // A handful of persistent host threads (MSAMD_PACK_THREADS, default 16; the process keeps them for its lifetime). One job at
 // a time: the element range is cut into chunks, every chunk into one piece per worker; pieces are claimed in order, so
 // the chunks complete in order and the caller uploads chunk k while the workers narrow chunk k + 1.
-// the CPUs of the NUMA node that holds the page at `addr`, intersected with what this process may run on (empty: unknown)
-std::vector<int> cpus_near(const void* addr) {
-  std::vector<int> out;
-  int node = -1;
-#if defined(SYS_get_mempolicy)
-  if (!addr || syscall(SYS_get_mempolicy, &node, nullptr, 0UL, const_cast<void*>(addr), 3UL /* MPOL_F_NODE | MPOL_F_ADDR */) != 0) node = -1;
-#endif
-  if (node < 0) return out;
-  char path[96];
-  snprintf(path, sizeof(path), "/sys/devices/system/node/node%d/cpulist", node);
-  FILE* f = fopen(path, "r");
-  if (!f) return out;
-  char buf[4096];
-  const size_t got = fread(buf, 1, sizeof(buf) - 1, f);
-  fclose(f);
-  buf[got] = 0;
-  cpu_set_t allowed;
-  CPU_ZERO(&allowed);
-  if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return out;
-  for (char* p = buf; *p;) {  // "0-63,128-191"
-    char* e = nullptr;
-    long a = strtol(p, &e, 10);
-    if (e == p) break;
-    long b = a;
-    if (*e == '-') {
-      p = e + 1;
-      b = strtol(p, &e, 10);
-    }
-    for (long c = a; c <= b && c < CPU_SETSIZE; c++)
-      if (CPU_ISSET((int)c, &allowed)) out.push_back((int)c);
-    p = *e == ',' ? e + 1 : e;
-    if (*e != ',') break;
-  }
-  return out;
-}
-
 class PackPool {
  public:
   // One pool per DEVICE (created on first use, never destroyed): a process that drives several GPUs from thread ranks
   // (ms_comm_local_*, `bench.py --gpus N` without a launcher) narrows every rank's trace at the same time instead of one job
   // after the other - a pool runs one job at a time. Contexts that share a device share its pool, as before.
-  // `near`: an address inside the first trace that will be narrowed. With MSAMD_PACK_AFFINITY=1 the workers are kept on
-  // the NUMA node that holds it; by default the scheduler places them
-  static PackPool* get(int device, const void* near = nullptr) {
+  static PackPool* get(int device) {
     static std::mutex mu;
     static std::map<int, PackPool*> pools;
     static const int n_threads = []() {
@@ -595,37 +553,25 @@ class PackPool {
     std::lock_guard<std::mutex> lk(mu);
     auto it = pools.find(device);
     if (it != pools.end()) return it->second;
-    // (measured: left to the scheduler the workers do as well or better - 6.99 against 7.34 ms per proof on one box of the
-    // pool, a tie on another; confining sixteen busy threads to the node of the trace crowds the runtime's own threads there.
-    // Polling workers between proofs instead of sleeping ones was worse still: 12-19 ms stalls every twenty proofs.)
-    PackPool* p = new PackPool(n_threads, getenv("MSAMD_PACK_AFFINITY") ? cpus_near(near) : std::vector<int>());
+    // (the workers are left to the scheduler: confined to the NUMA node of the trace they were measured no faster, 7.34 against
+    // 6.99 ms per proof on one box and a tie on another. Polling workers between proofs instead of sleeping ones was worse still: 12-19 ms stalls every twenty proofs.)
+    PackPool* p = new PackPool(n_threads);
     pools[device] = p;
     return p;
   }
   static constexpr size_t MAX_CHUNKS = 64, MAX_SUB = 128;
   size_t n_chunks = 0;
   // starts narrowing in[0 .. cnt) into out; chunk k covers elements [chunk_begin(k), chunk_begin(k + 1))
-  // (run_words != 0, "row groups": `in` is a sequence of blocks of run_stride words and chunk k is made of the k-th run of
-  // run_words words of every block, packed back to back: out[chunk_begin(k) + m * run_words + i] = in[m * run_stride + k * run_words + i].
-  // run_stride = chunks * run_words, cnt a multiple of run_stride.)
-  void start(const u64* in, uint8_t* out, unsigned pb, size_t cnt, size_t chunks, size_t run_words = 0) {
+  void start(const u64* in, uint8_t* out, unsigned pb, size_t cnt, size_t chunks) {
     job_mu_.lock();  // one job at a time (contexts on other threads wait here); released by finish()
     std::unique_lock<std::mutex> lk(mu_);
     done_cv_.wait(lk, [&] { return busy_ == 0; });  // the previous job's last workers have left (finish() does not wait for them)
     in_ = in, out_ = out, pb_ = pb, cnt_ = cnt;
     caller_ = std::this_thread::get_id();
     straggle_us_ = getenv("MSAMD_PACK_STRAGGLE_US") ? (unsigned)atoi(getenv("MSAMD_PACK_STRAGGLE_US")) : 0;  // (per job: tests flip it)
-    wait_all_ = getenv("MSAMD_PACK_WAIT_ALL") != nullptr;
     n_chunks = std::max<size_t>(1, std::min(chunks, MAX_CHUNKS));
-    run_words_ = run_words;
-    if (run_words) {
-      per_chunk_ = cnt / n_chunks;
-      run_stride_ = n_chunks * run_words;
-      runs_per_chunk_ = cnt / run_stride_;
-    } else {
-      per_chunk_ = ((cnt + n_chunks - 1) / n_chunks + 63) & ~size_t(63);
-      n_chunks = (cnt + per_chunk_ - 1) / per_chunk_;
-    }
+    per_chunk_ = ((cnt + n_chunks - 1) / n_chunks + 63) & ~size_t(63);
+    n_chunks = (cnt + per_chunk_ - 1) / per_chunk_;
     next_.store(0);
     acc_.store(0);
     nsub_ = std::min<size_t>(2 * threads_.size(), MAX_SUB);  // pieces per chunk
@@ -647,7 +593,7 @@ class PackPool {
       if (next_.load(std::memory_order_relaxed) >= (k + 1) * nsub_) {  // every piece of this chunk has a taker
         const double now = now_ms();
         if (all_claimed_at == 0) all_claimed_at = now;
-        if (now - all_claimed_at > 0.03 && !wait_all_) {  // 30 us: a healthy worker finishes a piece in 3-5 us
+        if (now - all_claimed_at > 0.03) {  // 30 us: a healthy worker finishes a piece in 3-5 us
           for (size_t sub = 0; sub < nsub_ && left_[k].load(std::memory_order_acquire) != 0; sub++)
             if (state_[k * nsub_ + sub].load(std::memory_order_acquire) != 2) work_piece(k * nsub_ + sub, true);  // (claimed: in work, or its worker not even started)
           continue;
@@ -660,10 +606,7 @@ class PackPool {
   // the job is over for its caller. Workers that are late (still waking up, or descheduled inside a piece the caller has redone)
   // leave on their own: the next start() and quiesce() wait for them (so a SECOND large trace of the same proof still waits for
   // the first one's late worker: one job at a time)
-  void finish() {
-    if (wait_all_) quiesce();  // MSAMD_PACK_WAIT_ALL=1: as before round 4's last change (every worker checks out, no second taker)
-    job_mu_.unlock();
-  }
+  void finish() { job_mu_.unlock(); }
   // no worker is inside a job (the buffers of finished jobs may be freed)
   void quiesce() {
     std::unique_lock<std::mutex> lk(mu_);
@@ -671,21 +614,13 @@ class PackPool {
   }
   struct Job {  // start ... finish, also when an error unwinds the caller
     PackPool& p;
-    Job(PackPool& pool, const u64* in, uint8_t* out, unsigned pb, size_t cnt, size_t chunks, size_t run_words = 0) : p(pool) {
-      p.start(in, out, pb, cnt, chunks, run_words);
-    }
+    Job(PackPool& pool, const u64* in, uint8_t* out, unsigned pb, size_t cnt, size_t chunks) : p(pool) { p.start(in, out, pb, cnt, chunks); }
     ~Job() { p.finish(); }
   };
 
  private:
-  PackPool(int n, const std::vector<int>& cpus) {
+  explicit PackPool(int n) {
     for (int i = 0; i < n; i++) threads_.emplace_back([this]() { run(); });
-    if ((int)cpus.size() >= n) {
-      cpu_set_t set;
-      CPU_ZERO(&set);
-      for (int c : cpus) CPU_SET(c, &set);
-      for (auto& t : threads_) (void)pthread_setaffinity_np(t.native_handle(), sizeof(set), &set);  // best effort
-    }
     for (auto& t : threads_) t.detach();
   }
   // claims the next piece of the job and narrows it; false = every piece has been claimed
@@ -705,17 +640,10 @@ class PackPool {
         std::this_thread::sleep_for(std::chrono::microseconds(straggle_us_));
     }
     u64 acc = 0;
-    if (run_words_) {
-      const size_t per = (runs_per_chunk_ + nsub_ - 1) / nsub_;
-      const size_t m0 = std::min(runs_per_chunk_, sub * per), m1 = std::min(runs_per_chunk_, m0 + per);
-      for (size_t m = m0; m < m1; m++)
-        acc |= narrow_range(in_ + m * run_stride_ + k * run_words_, out_ + (k * per_chunk_ + m * run_words_) * pb_, pb_, run_words_);
-    } else {
-      const size_t b = chunk_begin(k), e = chunk_begin(k + 1);
-      const size_t piece = (((e - b) + nsub_ - 1) / nsub_ + 7) & ~size_t(7);
-      const size_t lo = std::min(e, b + sub * piece), hi = std::min(e, lo + piece);
-      if (hi > lo) acc = narrow_range(in_ + lo, out_ + lo * pb_, pb_, hi - lo);
-    }
+    const size_t b = chunk_begin(k), e = chunk_begin(k + 1);
+    const size_t piece = (((e - b) + nsub_ - 1) / nsub_ + 7) & ~size_t(7);
+    const size_t lo = std::min(e, b + sub * piece), hi = std::min(e, lo + piece);
+    if (hi > lo) acc = narrow_range(in_ + lo, out_ + lo * pb_, pb_, hi - lo);
     if (acc) acc_.fetch_or(acc);
     if (state_[it].exchange(2, std::memory_order_acq_rel) != 2) left_[k].fetch_sub(1, std::memory_order_release);
   }
@@ -744,11 +672,9 @@ class PackPool {
   uint8_t* out_ = nullptr;
   unsigned pb_ = 1;
   size_t cnt_ = 0, per_chunk_ = 0, nsub_ = 1;
-  size_t run_words_ = 0, run_stride_ = 0, runs_per_chunk_ = 0;
   std::atomic<uint8_t> state_[MAX_CHUNKS * MAX_SUB];  // per piece: 0 unclaimed, 1 in work, 2 done
   std::thread::id caller_;
   unsigned straggle_us_ = 0;  // MSAMD_PACK_STRAGGLE_US (diagnostics)
-  bool wait_all_ = false;
   std::atomic<size_t> next_{0};
   std::atomic<u64> acc_{0};
   std::atomic<int> left_[MAX_CHUNKS];
@@ -809,10 +735,7 @@ std::unique_ptr<HWitness> witness_create_host(HSystem& sys, const u64* const* tr
   w->h_packed.assign(C, nullptr);
   size_t pack_min = size_t(4) << 20;  // below this the plain upload takes less than waking the threads
   if (const char* e = getenv("MSAMD_PACK_MIN_BYTES")) pack_min = (size_t)atoll(e);
-  const void* first_trace = nullptr;  // the tallest one
-  for (size_t ci = 0, best = 0; ci < C; ci++)
-    if (heights[ci] > best && traces[ci]) first_trace = traces[ci], best = heights[ci];
-  const bool may_pack = !getenv("MSAMD_NO_PACK") && PackPool::get(ctx.device, first_trace) != nullptr;
+  const bool may_pack = !getenv("MSAMD_NO_PACK") && PackPool::get(ctx.device) != nullptr;
   for (size_t ci = 0; ci < C; ci++) {
     const HCircuit& c = sys.circuits[ci];
     const size_t h = heights[ci];
@@ -900,17 +823,6 @@ struct HostUpload {
   Ctx& ctx;
   bool on = false;
   bool skip_claims = false;  // the multi-rank prover uploads per-rank slices of the claims itself
-  // Row groups (plain prover only, opt-in: MSAMD_ROW_GROUPS=1). A transform needs every row of a column, so with chunks of
-  // consecutive rows nothing of stage 1 can start before the last chunk has landed. The first pass of the inverse transform,
-  // though, works on 4096-row tiles of the bit-reversed storage, and tile t holds the natural rows r with r mod 2^T = rev_T(t),
-  // T = log2 h - 12: a chunk made of the rows whose residue has k in its top three bits - runs of 2^(T-3) consecutive rows
-  // every 2^T - completes the tiles t = 8 i + rev3(k). So chunk k is narrowed, pulled (scattered back to its rows: stage 2 reads
-  // the row-major trace), transposed and taken through that first pass while the host narrows chunk k + 1, and stage 1 starts
-  // at the second pass: 0.12 ms of kernels leave the critical path. Measured (2^20 x 14, 32-row runs of 3.5 KB every 28 KB):
-  // the HOST side loses more than that - sixteen threads narrow the trace in 0.39 ms from consecutive rows and in 0.52-0.59 ms
-  // from such runs (tools/micro/pack_runs.cpp; 0.43 ms only at 512-row runs, which would need a first pass of 8 levels), the
-  // last chunk is queued at 0.94-1.00 ms instead of 0.41-0.48, and the step is 0.05-0.2 ms SLOWER. Hence off by default.
-  bool row_groups = false;
   HostUpload(HWitness& wit, Ctx& c) : w(wit), ctx(c) {}
   // does stage 2 of this circuit run from the uploaded trace (stage2_terms_trace_jit)?
   bool fused(size_t ci) const {
@@ -924,7 +836,6 @@ struct HostUpload {
       if (!e) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     st.clear();
     st.traces.resize(C);
-    st.evals.resize(C);
     st.mult.resize(C);
     st.args.resize(C);
     // buffers first: pool blocks handed out here may still be in use by kernels queued earlier on ctx.stream
@@ -932,14 +843,7 @@ struct HostUpload {
     HIP_CHECK(hipStreamWaitEvent(ctx.copy_stream, ctx.copy_ev[3], 0));
     ctx.side_config();
     ctx.copy_delay();  // (diagnostics: MSAMD_COPY_DELAY_US)
-    std::vector<DBuf<uint8_t>> narrow(C);  // released when the proof's uploads have been waited for (the destructor's sync)
-    bool used_second = false;
     HIP_CHECK(hipStreamWaitEvent(ctx.claims_stream, ctx.copy_ev[3], 0));  // (pool blocks may still be in use by earlier kernels)
-    // The claims (42 MB at the bench size) are needed when the stage-1 tree is hashed, 0.8 ms after the trace has landed, and
-    // take 0.75 ms of the link: behind the trace's chunks on the copy stream they arrive just in time (kernel-only rocprofv3
-    // timeline: claims_words_k starts with the leaf hashing). MSAMD_CLAIMS_OWN_STREAM=1 starts them at once on a stream of
-    // their own, as DMA copies beside the chunks' pulling kernels - measured WORSE (6.9 against 6.4 ms per step): the link is the
-    // narrow upload's bottleneck, and what the claims take of it early delays the trace, which is on the critical path.
     const size_t n_claims = w.claim_offsets.size() - 1, tot = w.claim_data.size();
     // Uploads read the caller's page-locked ranges (HWitness::pin). Where a range could not be locked, the words go through the
     // context's bounce buffer instead of an asynchronous copy from pageable memory (Ctx::bounce_h2d has the reason)
@@ -949,18 +853,6 @@ struct HostUpload {
       else
         ctx.bounce_h2d(dst, src, bytes, s);
     };
-    static const bool claims_own_stream = getenv("MSAMD_CLAIMS_OWN_STREAM") != nullptr;
-    auto upload_claims = [&](hipStream_t s) {
-      st.claim_offsets = DBuf<u64>(ctx, n_claims + 1);
-      st.claim_data = DBuf<u64>(ctx, std::max<size_t>(tot, 1));
-      from_caller(st.claim_offsets.p, w.claim_offsets.data(), (n_claims + 1) * 8, s);
-      if (tot) from_caller(st.claim_data.p, w.claim_data.data(), tot * 8, s);
-      HIP_CHECK(hipEventRecord(st.ev[2], s));
-    };
-    if (!skip_claims && claims_own_stream) {
-      HIP_CHECK(hipStreamWaitEvent(ctx.claims_stream, ctx.copy_ev[3], 0));  // (the pool blocks may still be in use, as above)
-      upload_claims(ctx.claims_stream);
-    }
     for (size_t ci = 0; ci < C; ci++) {
       const HCircuit& c = sys.circuits[ci];
       const size_t h = w.heights[ci];
@@ -971,69 +863,27 @@ struct HostUpload {
       PackPool* pool = pb && !w.prefetch ? PackPool::get(ctx.device) : nullptr;  // (a prefetch already travels behind the running proof)
       bool sent = false;
       if (pool) {
-        // the host threads narrow chunk k + 1 while chunk k crosses the link; the device widens the whole trace afterwards
-        static const bool pull = !getenv("MSAMD_NO_PULL");  // MSAMD_NO_PULL=1: DMA copy into a staging buffer + widening launch
-        static const bool two_streams = getenv("MSAMD_PULL_TWO_STREAMS") != nullptr;  // (measured: no difference, 6.03-6.16 ms either way)
-        if (!pull) narrow[ci] = DBuf<uint8_t>(ctx, cnt * pb);
-        const bool want_groups = getenv("MSAMD_ROW_GROUPS") != nullptr;  // (read per proof: tests flip it)
-        const unsigned logh = log2_strict(h);
-        const bool groups = row_groups && pull && !two_streams && want_groups && (size_t(1) << logh) == h && logh >= 19 && cnt < (size_t(1) << 35) &&
-                            ctx.stream == ctx.main_stream;
-        if (groups) {
-          const size_t T = logh - 12, run_rows = size_t(1) << (T - 3), run_words = run_rows * c.main_width, run_stride = run_words * 8;
-          st.evals[ci] = DBuf<u64>(ctx, cnt);
-          PackPool::Job job(*pool, w.h_traces[ci], w.h_packed[ci], pb, cnt, 8, run_words);
-          sent = true;
-          auto first_pass = [&](unsigned k) {  // group k has landed: transposed and through the first pass on the main stream
-            HIP_CHECK(hipStreamWaitEvent(ctx.stream, ctx.group_event(k), 0));
-            transpose_in_rows_part(ctx, st.traces[ci].p, st.evals[ci].p, h, c.main_width, k);
-            ntt_dit_first_pass_part(ctx, st.evals[ci].p, logh, c.main_width, true, bitrev32(k, 3));
-          };
-          for (unsigned k = 0; k < 8; k++) {
-            if (!pool->wait_chunk(k)) {  // a value outgrew the width found at creation: the plain path below
-              sent = false;
-              break;
-            }
-            if (k == 0) g_probes.mark("narrow upload: first chunk ready");
-            pull_widen_runs(w.h_packed[ci] + pool->chunk_begin(k) * pb, pb, cnt / 8, st.traces[ci].p + k * run_words, run_words, run_stride, ctx.copy_stream);
-            HIP_CHECK(hipEventRecord(ctx.group_event(k), ctx.copy_stream));
-            if (k) first_pass(k - 1);  // (behind the pull: the link must not wait for this thread's launches)
+        // The host threads narrow chunk k + 1 while chunk k crosses the link. Measured and removed: DMA copies into a staging
+        // buffer with a widening launch behind each (6.57 against 6.17 ms per step), the pulls on two streams in turn (equal),
+        // and chunks of row groups that let the inverse transform's first pass start early (0.05-0.2 ms per step slower).
+        static const size_t n_chunks = getenv("MSAMD_PACK_CHUNKS") ? (size_t)atoi(getenv("MSAMD_PACK_CHUNKS")) : 8;
+        PackPool::Job job(*pool, w.h_traces[ci], w.h_packed[ci], pb, cnt, n_chunks);
+        sent = true;
+        for (size_t k = 0; k < pool->n_chunks; k++) {
+          if (!pool->wait_chunk(k)) {  // a value outgrew the width found at creation: the plain path below
+            sent = false;
+            break;
           }
-          if (sent) first_pass(7);
-          g_probes.mark("narrow upload: last chunk queued");
-          if (!sent) st.evals[ci].reset();  // (what the launches above wrote is abandoned; the block is reused behind them)
-        } else {
-          static const size_t n_chunks = getenv("MSAMD_PACK_CHUNKS") ? (size_t)atoi(getenv("MSAMD_PACK_CHUNKS")) : 8;
-          PackPool::Job job(*pool, w.h_traces[ci], w.h_packed[ci], pb, cnt, n_chunks);
-          sent = true;
-          for (size_t k = 0; k < pool->n_chunks; k++) {
-            if (!pool->wait_chunk(k)) {  // a value outgrew the width found at creation: the plain path below
-              sent = false;
-              break;
-            }
-            if (k == 0) g_probes.mark("narrow upload: first chunk ready");
-            const size_t b = pool->chunk_begin(k), e = pool->chunk_begin(k + 1);
-            if (pull) {  // ONE launch per chunk: the kernel reads the pinned narrow words over the link and writes 64-bit words
-              // (two streams in turn: the next chunk's first requests leave while this chunk's last ones drain)
-              const bool second = two_streams && (k & 1);
-              pull_widen_words(w.h_packed[ci] + b * pb, pb, e - b, st.traces[ci].p + b, second ? ctx.claims_stream : ctx.copy_stream);
-              used_second = used_second || second;
-            } else {
-              HIP_CHECK(hipMemcpyAsync(narrow[ci].p + b * pb, w.h_packed[ci] + b * pb, (e - b) * pb, hipMemcpyHostToDevice, ctx.copy_stream));
-              widen_words(narrow[ci].p + b * pb, pb, e - b, st.traces[ci].p + b, ctx.copy_stream);  // behind its chunk: only the last one is exposed
-            }
-          }
-          g_probes.mark("narrow upload: last chunk queued");
+          if (k == 0) g_probes.mark("narrow upload: first chunk ready");
+          const size_t b = pool->chunk_begin(k), e = pool->chunk_begin(k + 1);
+          // ONE launch per chunk: the kernel reads the pinned narrow words over the link and writes 64-bit words
+          pull_widen_words(w.h_packed[ci] + b * pb, pb, e - b, st.traces[ci].p + b, ctx.copy_stream);
         }
+        g_probes.mark("narrow upload: last chunk queued");
       }
       if (!sent) from_caller(st.traces[ci].p, w.h_traces[ci], cnt * 8, ctx.copy_stream);
     }
-    if (used_second) {  // the chunks pulled on the second stream are part of "the traces have arrived"
-      HIP_CHECK(hipEventRecord(ctx.copy_ev[2], ctx.claims_stream));
-      HIP_CHECK(hipStreamWaitEvent(ctx.copy_stream, ctx.copy_ev[2], 0));
-    }
     HIP_CHECK(hipEventRecord(st.ev[0], ctx.copy_stream));
-    st.narrow = std::move(narrow);
     st.has_host_lookups = false;
     for (size_t ci = 0; ci < C; ci++) {
       const HCircuit& c = sys.circuits[ci];
@@ -1048,8 +898,15 @@ struct HostUpload {
         if (!w.h_args[ci].empty()) from_caller(st.args[ci].p, w.h_args[ci].data(), w.h_args[ci].size() * 8, ctx.copy_stream);
       }
     }
-    if (!skip_claims && !claims_own_stream) upload_claims(ctx.copy_stream);
-    if (skip_claims) HIP_CHECK(hipEventRecord(st.ev[2], ctx.copy_stream));
+    // The claims (42 MB at the bench size) travel behind the trace's chunks and arrive just in time for the stage-1 tree's
+    // hashing: on a stream of their own from the start they were measured slower, 6.9 against 6.4 ms per step.
+    if (!skip_claims) {
+      st.claim_offsets = DBuf<u64>(ctx, n_claims + 1);
+      st.claim_data = DBuf<u64>(ctx, std::max<size_t>(tot, 1));
+      from_caller(st.claim_offsets.p, w.claim_offsets.data(), (n_claims + 1) * 8, ctx.copy_stream);
+      if (tot) from_caller(st.claim_data.p, w.claim_data.data(), tot * 8, ctx.copy_stream);
+    }
+    HIP_CHECK(hipEventRecord(st.ev[2], ctx.copy_stream));
     // SystemWitness::from_stage_1 (src/system.rs:244-328) as one kernel per circuit, from the traces just uploaded, queued on
     // the copy stream behind the copies: it writes 344 MB at config 2 and runs beside the transforms of stage 1 (which are
     // bound by the vector ALU) instead of in front of stage 2
@@ -1073,10 +930,8 @@ struct HostUpload {
       issue(w.stage[w.cur]);
     HWitness::Staged& st = w.stage[w.cur];
     // the proof reads through the witness's usual members
-    w.early_evals.resize(st.traces.size());
     for (size_t ci = 0; ci < st.traces.size(); ci++) {
       w.traces[ci] = std::move(st.traces[ci]);
-      w.early_evals[ci] = std::move(st.evals[ci]);
       w.lookups[ci].mult = std::move(st.mult[ci]);
       w.lookups[ci].args = std::move(st.args[ci]);
     }
@@ -1105,9 +960,7 @@ struct HostUpload {
     // prefetch queued behind them is then complete as well, which costs nothing: it is shorter than the proof)
     (void)hipStreamSynchronize(ctx.copy_stream);
     (void)hipStreamSynchronize(ctx.claims_stream);
-    w.stage[w.cur].narrow.clear();
     for (auto& t : w.traces) t.reset();
-    for (auto& t : w.early_evals) t.reset();
     for (auto& lk : w.lookups) {
       lk.mult.reset();
       lk.args.reset();
@@ -1166,7 +1019,6 @@ bool e2_same(E2 a, E2 b) { return a.c0 == b.c0 && a.c1 == b.c1; }
 // moment the host needs the values - returns every value; pcs_open then swaps the placeholders for them.
 struct SymbolicPoints {
   const E2* d_points = nullptr;
-  const u32* d_state = nullptr;  // 8 words: the challenger's input buffer behind the last point's sample (device), or null
   size_t n = 0;
   std::function<void(std::vector<E2>& values)> resolve;
   std::vector<int> next_log;  // per id: point id = point 0 times the generator of the subgroup of order 2^next_log[id] (-1: unrelated)
@@ -1252,16 +1104,9 @@ struct FriHead {
     return b;
   }
 };
-// FRI's transcript starts from a state that lies on the DEVICE (the opened values were absorbed there, open_alpha_k): fri_prove
-// takes it from d_state instead of uploading the host challenger's, and calls after_wait right behind its first wait - the
-// host catches up there (replays what the device did, checks it) before FRI's own steps are replayed.
-struct FriDeviceStart {
-  DBuf<uint32_t> d_state;
-  std::function<void()> after_wait;
-};
 void fri_prove(HSystem& sys, Challenger& ch, std::vector<DBuf<E2>>& inputs, unsigned log_gmax, const std::vector<GatherSeg>& input_segs,
                size_t input_qbytes, const InputShape& shape, const InputGather* remote, PW& fri_bytes, PhaseTrace& tr,
-               FriHead* head = nullptr, DTree* round0 = nullptr, FriDeviceStart* dstart = nullptr);
+               FriHead* head = nullptr, DTree* round0 = nullptr);
 
 // TwoAdicFriPcs::open + prove_fri; serialises the FriProof straight into `fri_bytes`.
 void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std::vector<OpenedRound>& opened, PW& fri_bytes,
@@ -1407,32 +1252,22 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
   }
   std::vector<E2> h_sums(std::max<size_t>(total_vals, 1));
   g_probes.mark("opened values queued");
-  // The opened values' transcript step on the DEVICE (open_alpha_k): with the outer transcript already there (`sym`) and FRI's
-  // rounds device-driven, the finishing factors, the absorption of every opened value, the batching challenge alpha, its powers
-  // and the reduced openings' coefficients and constants are one single-workgroup launch, and the proof's only wait is FRI's:
-  // the raw sums arrive with it, and the host then replays the outer transcript, finishes the sums itself, absorbs the values
-  // and compares its alpha with the device's. OPT-IN (MSAMD_DEV_OPENING=1): measured EQUAL to the host doing the step between
-  // two waits (5.58-5.61 against 5.51-5.57 ms per HBM-resident proof, A / B on one box): the 64 + 13 us the GPU idles at the
-  // opened-values wait are traded for a 25-30 us single-workgroup launch on the critical path and for the host's share of the
-  // step (finishing the sums, absorbing the values: ~30 us) moving behind the proof's last kernel.
-  const size_t fri_stop = (size_t(1) << lb) << prm.log_final_poly_len;
-  size_t n_entry_pairs = 0;
-  for (auto& r : rounds)
-    for (auto& pts : r.points) n_entry_pairs += pts.size();
-  const bool dev_open = sym && sym->d_state && gmax > fri_stop && prm.cap_height == 0 && prm.commit_pow_bits <= 16 && prm.max_log_arity == 1 &&
-                        32 + 16 * total_vals <= (size_t(256) << 10) && gw < (size_t(1) << 20) && n_entry_pairs <= 512 && !getenv("MSAMD_HOST_FRI") && getenv("MSAMD_DEV_OPENING");
-  auto finish_and_observe = [&]() {  // host: the opened values from the raw sums (points known), absorbed in round -> matrix -> point order
-    if (sym) {  // the host learns the points now (and replays the transcript that produced them)
-      std::vector<E2> values(sym->n);
-      sym->resolve(values);
-      auto swap_in = [&](E2& z) {
-        if (is_sym_point(z)) z = values[z.c0];
-      };
-      for (auto& z : upts) swap_in(z);
-      for (auto& r : rounds)
-        for (auto& pts : r.points)
-          for (auto& z : pts) swap_in(z);
-    }
+  // (the host does the opened values' transcript step between two waits. Built as one single-workgroup launch that left FRI's
+  // wait as the proof's only one, it was measured equal, 5.58-5.61 against 5.51-5.57 ms per HBM-resident proof, and removed)
+  ctx.d2h(h_sums.data(), d_sums.p, total_vals * sizeof(E2));
+  g_probes.mark("sync 4 (opened values)");
+  if (sym) {  // the host learns the points now (and replays the transcript that produced them)
+    std::vector<E2> values(sym->n);
+    sym->resolve(values);
+    auto swap_in = [&](E2& z) {
+      if (is_sym_point(z)) z = values[z.c0];
+    };
+    for (auto& z : upts) swap_in(z);
+    for (auto& r : rounds)
+      for (auto& pts : r.points)
+        for (auto& z : pts) swap_in(z);
+  }
+  {  // the opened values from the raw sums, absorbed in round -> matrix -> point order
     size_t off = 0;
     for (auto& r : rounds) {
       OpenedRound orr;
@@ -1454,101 +1289,62 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
       }
       opened.push_back(std::move(orr));
     }
-  };
-  E2 alpha = e2(0);
-  std::vector<E2> apow(gw + 1);
-  if (dev_open) {
-    ctx.d2h_queue(h_sums.data(), d_sums.p, total_vals * sizeof(E2));
-  } else {
-    ctx.d2h(h_sums.data(), d_sums.p, total_vals * sizeof(E2));
-    g_probes.mark("sync 4 (opened values)");
-    finish_and_observe();
-    tr.mark("bary_eval");
-    g_probes.mark("opened values observed");
-    alpha = ch.sample_ext();
-    apow[0] = e2(1);
-    for (size_t i = 1; i <= gw; i++) apow[i] = e2_mul(apow[i - 1], alpha);
   }
-  // reduced openings per LDE height; the opening points of one height are numbered locally (at most two). Everything but the
-  // coefficients and the constants K follows from the opening's SHAPE; those two come from alpha and the opened values - on the
-  // host here, or from open_alpha_k, which gets one OpenEntry per (matrix, point) saying where its inputs and outputs lie
+  tr.mark("bary_eval");
+  g_probes.mark("opened values observed");
+  const E2 alpha = ch.sample_ext();
+  std::vector<E2> apow(gw + 1);
+  apow[0] = e2(1);
+  for (size_t i = 1; i <= gw; i++) apow[i] = e2_mul(apow[i - 1], alpha);
+  // reduced openings per LDE height; the opening points of one height are numbered locally (at most two)
   std::vector<size_t> num_reduced(33, 0);
   std::vector<std::vector<DeepMat>> lists(33);
   std::vector<DeepPoints> hpts(33);
   std::vector<std::vector<size_t>> hpt_global(33);
   std::vector<char> present(33, 0);
-  std::vector<OpenEntry> entries;                        // dev_open: observe order
-  std::vector<std::pair<unsigned, size_t>> entry_mat;    // (height, index in lists[height]) of each entry's matrix
   constexpr size_t NEXT_MARK = size_t(1) << 62;
   for (auto& hp : hpts) memset(&hp, 0, sizeof(hp));
-  {
-    size_t sum_off = 0, out_off = 0;
-    for (size_t ri = 0; ri < rounds.size(); ri++) {
-      auto& r = rounds[ri];
-      for (size_t mi = 0; mi < r.data->ldes.size(); mi++) {
-        const DMat& m = r.data->ldes[mi];
-        unsigned lh = log2_strict(m.h);
-        present[lh] = 1;
-        auto& pts = r.points[mi];
-        if (pts.empty()) continue;
-        DeepMat dm;
-        memset(&dm, 0, sizeof(dm));
-        dm.d = m.d();
-        dm.w = (uint32_t)m.w;
-        dm.npoints = (uint32_t)pts.size();
-        for (size_t pi = 0; pi < pts.size(); pi++) {
-          // a "next" point is named by the first point's arrays plus a mark (all matrices of one height share g, so the pair
-          // (arrays, mark) identifies the point at this height)
-          const bool nx = pi == 1 && is_next[ri][mi];
-          const size_t gk = point_index(pts[nx ? 0 : pi]) | (nx ? NEXT_MARK : size_t(0));
-          size_t local = 0;
-          while (local < hpt_global[lh].size() && hpt_global[lh][local] != gk) local++;
-          if (local == hpt_global[lh].size()) {
-            if (local == 2) throw std::runtime_error("pcs_open: more than two opening points at one LDE height");
-            hpt_global[lh].push_back(gk);
-            hpts[lh].den[local] = dens[gk & ~NEXT_MARK].p;
-            hpts[lh].shift[local] = nx ? (uint32_t(1) << lb) : 0u;  // g = w_H^blowup
-            hpts[lh].K[local] = e2(0);
-            hpts[lh].n = (uint32_t)(local + 1);
-          }
-          const u64 cmul = nx ? gl_inv(gl_two_adic_generator(lh - lb)) : 1;  // 1 / (z g - x_j) = g^-1 / (z - x_sigma(j))
-          dm.pt[pi] = (uint32_t)local;
-          if (dev_open) {
-            const unsigned log_h = lh - lb;
-            const u64 s_pow = gl_exp_pow2(GL_GEN, log_h);
-            OpenEntry en;
-            memset(&en, 0, sizeof(en));
-            en.sum_off = (uint32_t)sum_off;
-            en.out_off = (uint32_t)out_off;
-            en.w = (uint32_t)m.w;
-            en.np = (uint32_t)pts.size();
-            en.p = (uint32_t)pi;
-            en.log_h = log_h;
-            if (!is_sym_point(pts[pi])) throw std::runtime_error("pcs_open: device opening needs device points");
-            en.point_id = (uint32_t)pts[pi].c0;
-            en.exp = (uint32_t)num_reduced[lh];
-            en.slot = (uint32_t)(2 * lh + local);
-            en.s_pow = s_pow;
-            en.dinv = gl_inv(gl_mul(s_pow, (u64(1) << log_h) % GL_P));
-            en.cmul = cmul;
-            entries.push_back(en);
-            entry_mat.emplace_back(lh, lists[lh].size());
-          } else {
-            E2 coeff = e2_pow(alpha, num_reduced[lh]);
-            E2 rz = e2(0);
-            const std::vector<E2>& ys = opened[ri][mi][pi];
-            for (size_t c = 0; c < m.w; c++) rz = e2_add(rz, e2_mul(apow[c], ys[c]));
-            coeff = e2_mul_base(coeff, cmul);
-            dm.coeff[pi] = coeff;
-            dm.coeff7[pi] = gl_mul(coeff.c1, GL_EXT_W);
-            hpts[lh].K[local] = e2_add(hpts[lh].K[local], e2_mul(coeff, rz));
-          }
-          num_reduced[lh] += m.w;
-          out_off += m.w;
+  for (size_t ri = 0; ri < rounds.size(); ri++) {
+    auto& r = rounds[ri];
+    for (size_t mi = 0; mi < r.data->ldes.size(); mi++) {
+      const DMat& m = r.data->ldes[mi];
+      unsigned lh = log2_strict(m.h);
+      present[lh] = 1;
+      auto& pts = r.points[mi];
+      if (pts.empty()) continue;
+      DeepMat dm;
+      memset(&dm, 0, sizeof(dm));
+      dm.d = m.d();
+      dm.w = (uint32_t)m.w;
+      dm.npoints = (uint32_t)pts.size();
+      for (size_t pi = 0; pi < pts.size(); pi++) {
+        // a "next" point is named by the first point's arrays plus a mark (all matrices of one height share g, so the pair
+        // (arrays, mark) identifies the point at this height)
+        const bool nx = pi == 1 && is_next[ri][mi];
+        const size_t gk = point_index(pts[nx ? 0 : pi]) | (nx ? NEXT_MARK : size_t(0));
+        size_t local = 0;
+        while (local < hpt_global[lh].size() && hpt_global[lh][local] != gk) local++;
+        if (local == hpt_global[lh].size()) {
+          if (local == 2) throw std::runtime_error("pcs_open: more than two opening points at one LDE height");
+          hpt_global[lh].push_back(gk);
+          hpts[lh].den[local] = dens[gk & ~NEXT_MARK].p;
+          hpts[lh].shift[local] = nx ? (uint32_t(1) << lb) : 0u;  // g = w_H^blowup
+          hpts[lh].K[local] = e2(0);
+          hpts[lh].n = (uint32_t)(local + 1);
         }
-        sum_off += pts.size() * m.w;
-        lists[lh].push_back(dm);
+        const u64 cmul = nx ? gl_inv(gl_two_adic_generator(lh - lb)) : 1;  // 1 / (z g - x_j) = g^-1 / (z - x_sigma(j))
+        dm.pt[pi] = (uint32_t)local;
+        E2 coeff = e2_pow(alpha, num_reduced[lh]);
+        E2 rz = e2(0);
+        const std::vector<E2>& ys = opened[ri][mi][pi];
+        for (size_t c = 0; c < m.w; c++) rz = e2_add(rz, e2_mul(apow[c], ys[c]));
+        coeff = e2_mul_base(coeff, cmul);
+        dm.coeff[pi] = coeff;
+        dm.coeff7[pi] = gl_mul(coeff.c1, GL_EXT_W);
+        hpts[lh].K[local] = e2_add(hpts[lh].K[local], e2_mul(coeff, rz));
+        num_reduced[lh] += m.w;
       }
+      lists[lh].push_back(dm);
     }
   }
   g_probes.mark("reduced-opening coefficients");
@@ -1557,7 +1353,7 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
   size_t n_mats = 0;
   for (auto& l : lists) n_mats += l.size();
   std::vector<uint8_t> deep_blob((gw + 1) * sizeof(E2) + n_mats * sizeof(DeepMat));
-  if (!dev_open) memcpy(deep_blob.data(), apow.data(), (gw + 1) * sizeof(E2));
+  memcpy(deep_blob.data(), apow.data(), (gw + 1) * sizeof(E2));
   std::vector<size_t> list_off(33, 0);
   {
     size_t off = (gw + 1) * sizeof(E2);
@@ -1571,44 +1367,9 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
   DBuf<uint8_t> d_deep(ctx, deep_blob.size());
   ctx.h2d(d_deep.p, deep_blob.data(), deep_blob.size());
   const E2* d_apow = reinterpret_cast<const E2*>(d_deep.p);
-  DBuf<E2> d_K, d_opened, d_alpha;
-  DBuf<uint32_t> d_fri_state;
-  DBuf<OpenEntry> d_entries;
-  DBuf<Digest> d_cvs;
-  E2 h_alpha_dev = e2(0);
-  if (dev_open) {
-    for (size_t e = 0; e < entries.size(); e++)
-      entries[e].mat = (uint32_t)((list_off[entry_mat[e].first] - (gw + 1) * sizeof(E2)) / sizeof(DeepMat) + entry_mat[e].second);
-    d_entries = DBuf<OpenEntry>(ctx, std::max<size_t>(entries.size(), 1));
-    ctx.h2d(d_entries.p, entries.data(), entries.size() * sizeof(OpenEntry));
-    d_K = DBuf<E2>(ctx, 66);
-    d_opened = DBuf<E2>(ctx, std::max<size_t>(total_vals, 1));
-    d_alpha = DBuf<E2>(ctx, 1);
-    d_fri_state = DBuf<uint32_t>(ctx, 8);
-    d_cvs = DBuf<Digest>(ctx, (32 + 16 * total_vals + 1023) / 1024);
-    OpenAlphaArgs oa;
-    memset(&oa, 0, sizeof(oa));
-    oa.entries = d_entries.p;
-    oa.n_entries = (uint32_t)entries.size();
-    oa.n_vals = (uint32_t)total_vals;
-    oa.gw = (uint32_t)gw;
-    oa.n_slots = 66;
-    oa.sums = d_sums.p;
-    oa.points = sym->d_points;
-    oa.state_in = sym->d_state;
-    oa.opened = d_opened.p;
-    oa.apow = reinterpret_cast<E2*>(d_deep.p);
-    oa.mats = reinterpret_cast<DeepMat*>(d_deep.p + (gw + 1) * sizeof(E2));
-    oa.K = d_K.p;
-    oa.state_out = d_fri_state.p;
-    oa.alpha_out = d_alpha.p;
-    oa.cv_scratch = d_cvs.p;
-    open_alpha(ctx, oa);
-    ctx.d2h_queue(&h_alpha_dev, d_alpha.p, sizeof(E2));
-  }
   std::vector<DBuf<E2>> inputs;  // descending height
   DTree fri_round0;              // the tallest vector is FRI's first committed matrix: its leaf layer is hashed where it is produced
-  if (use_side) ctx.side_fork();  // behind the upload of the alpha powers (and the launch that fills them)
+  if (use_side) ctx.side_fork();  // behind the upload of the alpha powers
   for (int lh = 32; lh >= 0; lh--) {
     if (!present[lh]) continue;
     size_t h = size_t(1) << lh;
@@ -1622,8 +1383,7 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
         merkle_alloc(ctx, fri_round0, h / 2);
         leaves = fri_round0.base();
       }
-      deep_reduce(ctx, lists[lh], hpts[lh], h, d_apow, ro.p, apow.data(), leaves, reinterpret_cast<const DeepMat*>(d_deep.p + list_off[lh]), 0, 0,
-                  dev_open ? d_K.p + 2 * lh : nullptr);
+      deep_reduce(ctx, lists[lh], hpts[lh], h, d_apow, ro.p, apow.data(), leaves, reinterpret_cast<const DeepMat*>(d_deep.p + list_off[lh]));
     }
     inputs.push_back(std::move(ro));
   }
@@ -1650,17 +1410,7 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
     shape.widths.push_back(std::move(widths));
     shape.nsib.push_back(t.cap_layer());
   }
-  FriDeviceStart dstart;
-  if (dev_open) {
-    dstart.d_state = std::move(d_fri_state);
-    dstart.after_wait = [&]() {  // FRI's wait has delivered the raw sums, the commitments and the device's challenges
-      finish_and_observe();
-      alpha = ch.sample_ext();
-      if (!e2_same(alpha, h_alpha_dev)) throw std::runtime_error("the device transcript's batching challenge differs from the host challenger's");
-      g_probes.mark("opened values observed");
-    };
-  }
-  fri_prove(sys, ch, inputs, log_gmax, segs, out_off, shape, nullptr, fri_bytes, tr, nullptr, &fri_round0, dev_open ? &dstart : nullptr);
+  fri_prove(sys, ch, inputs, log_gmax, segs, out_off, shape, nullptr, fri_bytes, tr, nullptr, &fri_round0);
 }
 
 // prove_fri (commit phase, final polynomial, query proof of work, query openings) over the reduced openings
@@ -1670,7 +1420,7 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
 // `remote`, called with the sampled indices and filling the same layout.
 void fri_prove(HSystem& sys, Challenger& ch, std::vector<DBuf<E2>>& inputs, unsigned log_gmax, const std::vector<GatherSeg>& input_segs,
                size_t input_qbytes, const InputShape& shape, const InputGather* remote, PW& fri_bytes, PhaseTrace& tr, FriHead* head,
-               DTree* round0, FriDeviceStart* dstart) {
+               DTree* round0) {
   Ctx& ctx = *sys.ctx;
   const unsigned head_rounds = head ? head->n_rounds : 0;
   if (head && !remote) throw std::runtime_error("FRI: head rounds need the remote gather");
@@ -1706,7 +1456,7 @@ void fri_prove(HSystem& sys, Challenger& ch, std::vector<DBuf<E2>>& inputs, unsi
   // fri_tree_build, then the round's binary folds with beta, beta^2, beta^4 .. read from the round's record; no fused rounds,
   // no single-workgroup tail (MSAMD_HOST_WIDE_FRI=1: host-driven, one synchronisation per round, as before).
   const bool wide = prm.max_log_arity > 1;
-  const bool dev_rounds = folded.n > stop && prm.cap_height == 0 && (dstart || ch.input.size() == 32) && prm.commit_pow_bits <= 16 &&
+  const bool dev_rounds = folded.n > stop && prm.cap_height == 0 && ch.input.size() == 32 && prm.commit_pow_bits <= 16 &&
                           (!wide || (!head && !getenv("MSAMD_HOST_WIDE_FRI"))) && !getenv("MSAMD_HOST_FRI");
   const unsigned log_final_height = lb + (unsigned)prm.log_final_poly_len;
   // p3-fri compute_log_arity_for_round: as far as max_log_arity allows without stepping over the next input or the final height
@@ -1717,7 +1467,6 @@ void fri_prove(HSystem& sys, Challenger& ch, std::vector<DBuf<E2>>& inputs, unsi
     if (la < 1) throw std::runtime_error("FRI: two inputs of one height");
     return la;
   };
-  if (dstart && !dev_rounds) throw std::runtime_error("FRI: a transcript that starts on the device needs device-driven rounds");
   // With a one-coefficient final polynomial the query phase's challenger work (observe the final polynomial, grind,
   // sample every index) also runs on the device and the openings are gathered from the device-side indices, so
   // the whole of FRI costs one host synchronisation; the host replay below checks witness and indices.
@@ -1740,9 +1489,7 @@ void fri_prove(HSystem& sys, Challenger& ch, std::vector<DBuf<E2>>& inputs, unsi
     } else {
       for (size_t l = folded.n; l > stop; l >>= 1) n_total++;
     }
-    if (dstart) {
-      d_state = std::move(dstart->d_state);  // the opened values were absorbed on the device: FRI goes on from that state
-    } else if (head && head->on_device) {
+    if (head && head->on_device) {
       d_state = std::move(head->d_state);  // the head rounds' challenger steps have run on the device: go on from their state
     } else {
       d_state = DBuf<uint32_t>(ctx, 8);
@@ -1976,7 +1723,6 @@ void fri_prove(HSystem& sys, Challenger& ch, std::vector<DBuf<E2>>& inputs, unsi
     ctx.d2h(fin.data(), fin_src, stop * sizeof(E2));  // the one synchronisation of the FRI phase
     g_probes.mark("sync 5 (FRI)");
     fin_hold.reset();
-    if (dstart && dstart->after_wait) dstart->after_wait();  // the host catches up with what the device did in front of FRI
     for (size_t k = 0; k < hrecs.size(); k++) {  // the rounds that ran on row shards, replayed first: they come first in the transcript
       Digest root;
       memcpy(root.b, hrecs[k].root, 32);
@@ -2195,7 +1941,6 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
 
   RoctxRange whole("stark/prove");
   HostUpload up(wit, ctx);  // host-resident witness: uploads start now and run beside the transcript set-up
-  up.row_groups = true;
   up.start();
   g_probes.mark("uploads issued");
   Challenger ch(sys.seed);
@@ -2318,8 +2063,7 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
     for (size_t pos : order) {
       const size_t ci = aidx[pos];
       SideScope sc(ctx, on_side[pos]);
-      ldes[pos] = lde_of_host_matrix(ctx, wit.traces[ci].p, wit.heights[ci], sys.circuits[ci].main_width, lb,
-                                     !on_side[pos] && ci < wit.early_evals.size() ? &wit.early_evals[ci] : nullptr);
+      ldes[pos] = lde_of_host_matrix(ctx, wit.traces[ci].p, wit.heights[ci], sys.circuits[ci].main_width, lb);
     }
     ctx.side_join();
     if (early_claims) {
@@ -2401,18 +2145,16 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
   // runs there, beside the long circuits' stage-2 kernels (the streams join in front of that commitment) and BEHIND the short
   // circuits' stage 2, which the side stream also carries: the sum is a quarter of a millisecond of few, long-running waves
   // (one per SIMD); in front of the short circuits it held their launches back until the long circuit's stage-2 trace was
-  // being written, and beside the long circuit's terms it cost that kernel 20 us (226 -> 206). MSAMD_CLAIMS_ACC_FIRST=1: the
-  // earlier order
+  // being written, and beside the long circuit's terms it cost that kernel 20 us (226 -> 206)
   const bool claims_on_device = n_claims > 256 || dev_outer;
   const bool claims_beside = claims_on_device && ctx.side_enabled && !getenv("MSAMD_CLAIMS_ACC_MAIN");
-  const bool claims_last = claims_beside && !getenv("MSAMD_CLAIMS_ACC_FIRST");
   auto claims_sum_launch = [&]() {
     if (claims_beside && !ctx.side_forked) ctx.side_fork();
     SideScope sc(ctx, claims_beside);
     claims_accumulator_dyn(ctx, wit.d_claim_data.p, wit.d_claim_offsets.p, n_claims, d_bg.p, d_tot.p);
   };
   if (claims_on_device) {
-    if (!claims_last) claims_sum_launch();
+    if (!claims_beside) claims_sum_launch();
   } else {
     E2 acc0 = e2(0);
     for (size_t i = 0; i < n_claims; i++) {
@@ -2437,7 +2179,7 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
     s2_evals[pos] = DBuf<u64>(ctx, n * c.stage2_width);
     stage2_circuit_dyn(ctx, sys, wit, ci, d_bg.p, s2_evals[pos].p, d_tot.p + 1 + pos);
   }
-  if (claims_last) claims_sum_launch();
+  if (claims_beside) claims_sum_launch();
   lap(1);
   t0 = now_ms();
   phase.next("stark/stage2_commit");
@@ -2587,7 +2329,6 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
     pt_zeta = sym_point(0);
     for (size_t pos = 0; pos < NA; pos++) pt_next[pos] = sym_point(id_of[pos]);
     sym.d_points = od.points.p;
-    sym.d_state = od.state.p + 20;
     sym.n = 1 + n_ld;
     sym.next_log.assign(1 + n_ld, -1);
     for (size_t k = 0; k < n_ld; k++) sym.next_log[1 + k] = (int)od.uniq_ld[k];

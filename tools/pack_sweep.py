@@ -1,5 +1,5 @@
 """Host-resident step time by the narrow upload's settings (each setting in a fresh process: the pack pool is created once per
-process): MSAMD_PACK_THREADS x MSAMD_PACK_CHUNKS, with and without the pulling kernel (MSAMD_NO_PULL).
+process): MSAMD_PACK_THREADS x MSAMD_PACK_CHUNKS.
   python tools/pack_sweep.py            (driver)
   python tools/pack_sweep.py child N    (one setting: N proofs, prints mean / min / median ms)"""
 import os
@@ -44,8 +44,6 @@ settings = []
 for threads in (16, 24, 32, 48, 64):
     for chunks in (8, 16, 32):
         settings.append({"MSAMD_PACK_THREADS": str(threads), "MSAMD_PACK_CHUNKS": str(chunks)})
-settings.append({"MSAMD_PACK_THREADS": "16", "MSAMD_PACK_CHUNKS": "8", "MSAMD_NO_PULL": "1"})
-settings.append({"MSAMD_PACK_THREADS": "32", "MSAMD_PACK_CHUNKS": "16", "MSAMD_NO_PULL": "1"})
 for extra in settings:
     env = dict(os.environ)
     env.update(extra)
