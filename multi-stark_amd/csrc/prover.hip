@@ -20,6 +20,7 @@
 
 #include "host.h"
 #include "lookup_params.h"
+#include "open_plan.h"
 #include "quotient_params.h"
 
 namespace msamd {
@@ -1011,20 +1012,16 @@ struct OpenRound {
   std::vector<std::vector<E2>> points;
 };
 
-bool e2_same(E2 a, E2 b) { return a.c0 == b.c0 && a.c1 == b.c1; }
-
 // Opening points that only the DEVICE knows while the opening's first kernels are queued (the device transcript sampled
-// zeta, outer.hip): a point is named by a placeholder (sym_point(id): c1 is not a canonical field element, so it never equals
-// a real point), its value lies at d_points[id], and `resolve` - called right after the opened-value read-back, the first
-// moment the host needs the values - returns every value; pcs_open then swaps the placeholders for them.
+// zeta, outer.hip): a point is named by a placeholder (open_plan.h: sym_point), its value lies at d_points[id], and `resolve` -
+// called right after the opened-value read-back, the first moment the host needs the values - returns every value; pcs_open
+// then swaps the placeholders for them.
 struct SymbolicPoints {
   const E2* d_points = nullptr;
   size_t n = 0;
   std::function<void(std::vector<E2>& values)> resolve;
   std::vector<int> next_log;  // per id: point id = point 0 times the generator of the subgroup of order 2^next_log[id] (-1: unrelated)
 };
-inline E2 sym_point(size_t id) { return e2((u64)id, ~u64(0)); }
-inline bool is_sym_point(E2 z) { return z.c1 == ~u64(0); }
 
 // MSAMD_TRACE=1: synchronise and print the wall time of each phase of the opening (diagnostics only)
 struct PhaseTrace {
@@ -1159,24 +1156,17 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
         }
     }
   // unique opening points and the tallest matrix opened at each
-  std::vector<E2> upts;
-  std::vector<size_t> uh;
-  auto point_index = [&](E2 z) -> size_t {
-    for (size_t i = 0; i < upts.size(); i++)
-      if (e2_same(upts[i], z)) return i;
-    upts.push_back(z);
-    uh.push_back(0);
-    return upts.size() - 1;
-  };
+  OpenPoints op;
   for (size_t ri = 0; ri < rounds.size(); ri++) {
     auto& r = rounds[ri];
     for (size_t mi = 0; mi < r.data->ldes.size(); mi++)
       for (size_t pi = 0; pi < r.points[mi].size(); pi++) {
         if (pi == 1 && is_next[ri][mi]) continue;  // read through the first point's arrays
-        size_t k = point_index(r.points[mi][pi]);
-        uh[k] = std::max(uh[k], r.data->ldes[mi].h);
+        op.note(r.points[mi][pi], r.data->ldes[mi].h);
       }
   }
+  const std::vector<E2>& upts = op.upts;
+  const std::vector<size_t>& uh = op.uh;
   // short matrices beside tall ones: their launches go to the side stream (see prove()), queued behind the tall ones'
   ctx.side_config();
   const size_t short_h = size_t(1) << (ctx.side_max_log + lb);
@@ -1233,8 +1223,8 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
         int np = (int)pts.size();
         if ((int)(use_side && m.h <= short_h) == pass) {
           const bool nx = is_next[ri][mi];
-          const E2* d0 = xdens[point_index(pts[0])].p;
-          const E2* d1 = np == 2 && !nx ? xdens[point_index(pts[1])].p : d0;
+          const E2* d0 = xdens[op.index(pts[0])].p;
+          const E2* d1 = np == 2 && !nx ? xdens[op.index(pts[1])].p : d0;
           if (batch_bary) {
             specs.push_back(BarySpec{m.d(), m.h, m.w, log2_strict(m.h) - lb, d0, d1, np, d_sums.p + off, nx});
           } else {
@@ -1259,13 +1249,9 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
   if (sym) {  // the host learns the points now (and replays the transcript that produced them)
     std::vector<E2> values(sym->n);
     sym->resolve(values);
-    auto swap_in = [&](E2& z) {
-      if (is_sym_point(z)) z = values[z.c0];
-    };
-    for (auto& z : upts) swap_in(z);
+    op.resolve(values);
     for (auto& r : rounds)
-      for (auto& pts : r.points)
-        for (auto& z : pts) swap_in(z);
+      for (auto& pts : r.points) swap_in(pts, values);
   }
   {  // the opened values from the raw sums, absorbed in round -> matrix -> point order
     size_t off = 0;
@@ -1273,19 +1259,10 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
       OpenedRound orr;
       for (size_t mi = 0; mi < r.data->ldes.size(); mi++) {
         const DMat& m = r.data->ldes[mi];
-        auto& pts = r.points[mi];
-        std::vector<std::vector<E2>> per_point;
-        if (!pts.empty()) {
-          int np = (int)pts.size();
-          std::vector<E2> ys(np * m.w);
-          bary_finish(&h_sums[off], m.w, log2_strict(m.h) - lb, pts.data(), np, ys.data());
-          off += np * m.w;
-          for (int p = 0; p < np; p++) {
-            per_point.emplace_back(ys.begin() + p * m.w, ys.begin() + (p + 1) * m.w);
-            for (auto& y : per_point.back()) ch.observe_ext(y);
-          }
-        }
-        orr.push_back(std::move(per_point));
+        orr.push_back(finish_opened(h_sums.data() + off, m.w, log2_strict(m.h) - lb, r.points[mi]));
+        off += r.points[mi].size() * m.w;
+        for (auto& pt : orr.back())
+          for (auto& y : pt) ch.observe_ext(y);
       }
       opened.push_back(std::move(orr));
     }
@@ -1293,60 +1270,17 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
   tr.mark("bary_eval");
   g_probes.mark("opened values observed");
   const E2 alpha = ch.sample_ext();
-  std::vector<E2> apow(gw + 1);
-  apow[0] = e2(1);
-  for (size_t i = 1; i <= gw; i++) apow[i] = e2_mul(apow[i - 1], alpha);
-  // reduced openings per LDE height; the opening points of one height are numbered locally (at most two)
-  std::vector<size_t> num_reduced(33, 0);
-  std::vector<std::vector<DeepMat>> lists(33);
-  std::vector<DeepPoints> hpts(33);
-  std::vector<std::vector<size_t>> hpt_global(33);
-  std::vector<char> present(33, 0);
-  constexpr size_t NEXT_MARK = size_t(1) << 62;
-  for (auto& hp : hpts) memset(&hp, 0, sizeof(hp));
+  const std::vector<E2> apow = alpha_powers(alpha, gw);
+  // reduced openings per LDE height, in round -> matrix order
+  DeepPlan plan(op, dens, alpha, apow, lb);
   for (size_t ri = 0; ri < rounds.size(); ri++) {
     auto& r = rounds[ri];
     for (size_t mi = 0; mi < r.data->ldes.size(); mi++) {
       const DMat& m = r.data->ldes[mi];
-      unsigned lh = log2_strict(m.h);
-      present[lh] = 1;
-      auto& pts = r.points[mi];
-      if (pts.empty()) continue;
-      DeepMat dm;
-      memset(&dm, 0, sizeof(dm));
-      dm.d = m.d();
-      dm.w = (uint32_t)m.w;
-      dm.npoints = (uint32_t)pts.size();
-      for (size_t pi = 0; pi < pts.size(); pi++) {
-        // a "next" point is named by the first point's arrays plus a mark (all matrices of one height share g, so the pair
-        // (arrays, mark) identifies the point at this height)
-        const bool nx = pi == 1 && is_next[ri][mi];
-        const size_t gk = point_index(pts[nx ? 0 : pi]) | (nx ? NEXT_MARK : size_t(0));
-        size_t local = 0;
-        while (local < hpt_global[lh].size() && hpt_global[lh][local] != gk) local++;
-        if (local == hpt_global[lh].size()) {
-          if (local == 2) throw std::runtime_error("pcs_open: more than two opening points at one LDE height");
-          hpt_global[lh].push_back(gk);
-          hpts[lh].den[local] = dens[gk & ~NEXT_MARK].p;
-          hpts[lh].shift[local] = nx ? (uint32_t(1) << lb) : 0u;  // g = w_H^blowup
-          hpts[lh].K[local] = e2(0);
-          hpts[lh].n = (uint32_t)(local + 1);
-        }
-        const u64 cmul = nx ? gl_inv(gl_two_adic_generator(lh - lb)) : 1;  // 1 / (z g - x_j) = g^-1 / (z - x_sigma(j))
-        dm.pt[pi] = (uint32_t)local;
-        E2 coeff = e2_pow(alpha, num_reduced[lh]);
-        E2 rz = e2(0);
-        const std::vector<E2>& ys = opened[ri][mi][pi];
-        for (size_t c = 0; c < m.w; c++) rz = e2_add(rz, e2_mul(apow[c], ys[c]));
-        coeff = e2_mul_base(coeff, cmul);
-        dm.coeff[pi] = coeff;
-        dm.coeff7[pi] = gl_mul(coeff.c1, GL_EXT_W);
-        hpts[lh].K[local] = e2_add(hpts[lh].K[local], e2_mul(coeff, rz));
-        num_reduced[lh] += m.w;
-      }
-      lists[lh].push_back(dm);
+      plan.add(log2_strict(m.h), m.d(), 0, m.w, r.points[mi], is_next[ri][mi], opened[ri][mi]);
     }
   }
+  const auto& lists = plan.lists;
   g_probes.mark("reduced-opening coefficients");
   // the alpha powers and every height's matrix list cross in ONE copy (each copy is a launch of its own in the stream)
   static_assert(sizeof(DeepMat) % 8 == 0 && sizeof(E2) == 16, "the blob keeps both aligned");
@@ -1371,7 +1305,7 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
   DTree fri_round0;              // the tallest vector is FRI's first committed matrix: its leaf layer is hashed where it is produced
   if (use_side) ctx.side_fork();  // behind the upload of the alpha powers
   for (int lh = 32; lh >= 0; lh--) {
-    if (!present[lh]) continue;
+    if (!plan.present[lh]) continue;
     size_t h = size_t(1) << lh;
     SideScope sc(ctx, use_side && h <= short_h);
     DBuf<E2> ro(ctx, h);
@@ -1383,7 +1317,7 @@ void pcs_open(HSystem& sys, std::vector<OpenRound>& rounds, Challenger& ch, std:
         merkle_alloc(ctx, fri_round0, h / 2);
         leaves = fri_round0.base();
       }
-      deep_reduce(ctx, lists[lh], hpts[lh], h, d_apow, ro.p, apow.data(), leaves, reinterpret_cast<const DeepMat*>(d_deep.p + list_off[lh]));
+      deep_reduce(ctx, lists[lh], plan.hpts[lh], h, d_apow, ro.p, apow.data(), leaves, reinterpret_cast<const DeepMat*>(d_deep.p + list_off[lh]));
     }
     inputs.push_back(std::move(ro));
   }
@@ -2015,18 +1949,7 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
   // zeta are sampled in the stream and every launch up to the opened-value sums is queued without a host round trip; the
   // host challenger replays the steps when the commitments arrive with the opened values, and is the authority.
   const bool dev_outer = device_claims && outer_fits(ncap, NA) && !getenv("MSAMD_HOST_TRANSCRIPT");
-  struct OuterDev {
-    DBuf<Digest> digest;
-    DBuf<u32> state;  // 12 words behind gamma, 8 words behind alpha
-    DBuf<E2> accs, alpha, points;
-    DBuf<u32> lds;
-    DBuf<uint8_t> circuits;
-    std::vector<DBuf<uint8_t>> qdyn;  // per active circuit: QDyn, then the reversed alpha powers
-    Digest h_digest;
-    E2 h_bg[2], h_alpha;
-    std::vector<E2> h_points;
-    std::vector<unsigned> uniq_ld;  // the distinct trace heights: points[1 + k] = zeta * g(2^uniq_ld[k])
-  } od;
+  OuterDev od;
   DBuf<ChallengeBG> d_bg;
   if (device_claims) {
     s1_cap.assign(ncap, Digest());
@@ -2126,14 +2049,8 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
     d_prefix.reset();
   }
   E2 beta = e2(0), gamma = e2(0), alpha = e2(0), zeta = e2(0);
-  auto tx_beta_gamma = [&]() {
-    beta = ch.sample_ext();
-    ch.observe_ext(beta);
-    gamma = ch.sample_ext();
-    ch.observe_ext(gamma);
-  };
   if (!dev_outer) {
-    tx_beta_gamma();
+    tx_beta_gamma(ch, beta, gamma);
     d_bg = challenge_bg_upload(ctx, beta, gamma);
   }
   // initial accumulator from the claims (src/prover.rs:382-387). Nothing below needs the accumulators on the
@@ -2212,7 +2129,7 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
   std::vector<Digest> s2_cap, q_cap;
   E2 acc_initial = e2(0);
   std::vector<E2> accs;
-  auto tx_alpha = [&]() {  // src/prover.rs:382-433
+  auto host_alpha = [&]() {  // src/prover.rs:382-433
     acc_initial = h_tot[0];
     accs.clear();
     E2 acc = acc_initial;
@@ -2220,9 +2137,7 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
       acc = e2_add(acc, h_tot[1 + pos]);
       accs.push_back(acc);
     }
-    ch.observe_cap(s2_cap);
-    for (auto& a : accs) ch.observe_ext(a);
-    alpha = ch.sample_ext();
+    alpha = tx_alpha(ch, s2_cap, accs);
   };
   if (dev_outer) {
     s2_cap.assign(ncap, Digest());
@@ -2248,7 +2163,7 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
     s2_cap = merkle_cap(ctx, s2.tree);  // synchronises: h_tot is complete as well
     g_probes.mark("sync 2 (stage-2 cap)");
     lap(2);
-    tx_alpha();
+    host_alpha();
   }
 
   // ---- quotient (src/prover.rs:437-528)
@@ -2264,29 +2179,8 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
       SideScope sc(ctx, on_side[pos]);
       unsigned log_n = log_degrees[pos], log_q = log2_strict(c.quotient_degree());
       size_t n = size_t(1) << log_n, nq = n << log_q;
-      QuotientArgs qa;
-      if (sys.has_pre && sys.pre_indices[ci] >= 0) {
-        const DMat& pm = sys.pre_data.ldes[sys.pre_indices[ci]];
-        qa.pre = pm.d();
-        qa.pre_h = pm.h;
-      }
-      qa.s1 = s1.ldes[pos].d();
-      qa.s1_h = s1.ldes[pos].h;
-      qa.s2 = s2.ldes[pos].d();
-      qa.s2_h = s2.ldes[pos].h;
-      qa.log_n = log_n;
-      qa.log_q = log_q;
-      if (dev_outer) {
-        qa.dyn = reinterpret_cast<const QDyn*>(od.qdyn[pos].p);
-        qa.alpha_rev = reinterpret_cast<const E2*>(od.qdyn[pos].p + sizeof(QDyn));
-      } else {
-        const E2 four[4] = {beta, gamma, pos ? accs[pos - 1] : acc_initial, accs[pos]};
-        for (int k = 0; k < 4; k++) {
-          qa.publics[2 * k] = four[k].c0;
-          qa.publics[2 * k + 1] = four[k].c1;
-        }
-        qa.alpha = alpha;
-      }
+      QuotientArgs qa = fill_quotient_args(sys, ci, s1.ldes[pos], s2.ldes[pos], log_n, log_q, dev_outer ? od.qdyn[pos].p : nullptr);
+      if (!dev_outer) quotient_publics(qa, beta, gamma, pos ? accs[pos - 1] : acc_initial, accs[pos], alpha);
       DBuf<u64> qv(ctx, nq * 2);
       quotient_eval(ctx, c.prog, qa, qv.p);
       DMat lde;
@@ -2300,10 +2194,6 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
     commit_matrices(ctx, std::move(qldes), (unsigned)prm.cap_height, qd);
   }
   g_probes.mark("quotient queued");
-  auto tx_zeta = [&]() {
-    ch.observe_cap(q_cap);
-    zeta = ch.sample_ext();
-  };
   // zeta and zeta * g per trace height: values in host mode, placeholders for device values otherwise (pcs_open swaps them)
   E2 pt_zeta = e2(0);
   std::vector<E2> pt_next(NA);
@@ -2312,22 +2202,8 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
     q_cap.assign(ncap, Digest());
     const Digest* d_cap = dev_cap(qd.tree);
     ctx.d2h_queue(q_cap.data(), d_cap, ncap * sizeof(Digest));
-    std::vector<size_t> id_of(NA);
-    for (size_t pos = 0; pos < NA; pos++) {
-      size_t k = 0;
-      while (k < od.uniq_ld.size() && od.uniq_ld[k] != log_degrees[pos]) k++;
-      if (k == od.uniq_ld.size()) od.uniq_ld.push_back(log_degrees[pos]);
-      id_of[pos] = 1 + k;
-    }
+    zeta_placeholders(ctx, od, log_degrees, d_cap, ncap, od.state.p + 20, pt_zeta, pt_next);
     const size_t n_ld = od.uniq_ld.size();
-    od.lds = DBuf<u32>(ctx, n_ld);
-    ctx.h2d(od.lds.p, od.uniq_ld.data(), n_ld * sizeof(u32));
-    od.points = DBuf<E2>(ctx, 1 + n_ld);
-    od.h_points.assign(1 + n_ld, e2(0));
-    outer_zeta(ctx, od.state.p + 12, d_cap, ncap, od.lds.p, n_ld, od.points.p, od.state.p + 20);
-    ctx.d2h_queue(od.h_points.data(), od.points.p, (1 + n_ld) * sizeof(E2));
-    pt_zeta = sym_point(0);
-    for (size_t pos = 0; pos < NA; pos++) pt_next[pos] = sym_point(id_of[pos]);
     sym.d_points = od.points.p;
     sym.n = 1 + n_ld;
     sym.next_log.assign(1 + n_ld, -1);
@@ -2342,7 +2218,7 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
     // ---- opening (src/prover.rs:538-581)
     t0 = now_ms();
     phase.next("stark/fri_open");
-    tx_zeta();
+    zeta = tx_zeta(ch, q_cap);
     pt_zeta = zeta;
     for (size_t pos = 0; pos < NA; pos++) pt_next[pos] = e2_mul_base(zeta, gl_two_adic_generator(log_degrees[pos]));
   }
@@ -2395,16 +2271,10 @@ std::vector<uint8_t> prove(HSystem& sys, HWitness& wit, StageMs* times) {
   sym.resolve = [&](std::vector<E2>& values) {
     // everything queued since the stage-1 commitment has arrived: replay the transcript on the host and compare
     ch.flush_with(od.h_digest);
-    tx_beta_gamma();
-    tx_alpha();
-    tx_zeta();
-    bool same = e2_same(beta, od.h_bg[0]) && e2_same(gamma, od.h_bg[1]) && e2_same(alpha, od.h_alpha) && e2_same(zeta, od.h_points[0]);
-    values[0] = zeta;
-    for (size_t k = 0; k < od.uniq_ld.size(); k++) {
-      values[1 + k] = e2_mul_base(zeta, gl_two_adic_generator(od.uniq_ld[k]));
-      same = same && e2_same(values[1 + k], od.h_points[1 + k]);
-    }
-    if (!same) throw std::runtime_error("the device transcript's challenges differ from the host challenger's");
+    tx_beta_gamma(ch, beta, gamma);
+    host_alpha();
+    zeta = tx_zeta(ch, q_cap);
+    values = replayed_points(od, beta, gamma, alpha, zeta);
     PW h;
     write_header(h);
     if (h.b.size() != header_len) throw std::runtime_error("proof header changed length");

@@ -1,5 +1,6 @@
 // One proof over several GPUs (SURVEY §8e; BASELINE config 3): included at the end of prover.hip, inside namespace
-// msamd, so it shares the single-GPU prover's helpers. Every circuit is either "sharded" - owned by ONE rank, which
+// msamd, so it shares the single-GPU prover's helpers; the opening's host bookkeeping and the outer transcript's steps
+// are the ones prove() and pcs_open use (open_plan.h). Every circuit is either "sharded" - owned by ONE rank, which
 // computes its columns: LDE, stage-2 trace, quotient, opened values; a rank may own any number of circuits, of any
 // shapes - or "replicated": every rank computes it (small tables). Every commitment is ONE Merkle tree whose leaf i hashes row i of
 // ALL matrices (src/types.rs:82-83), so before hashing the ranks exchange row ranges: rank k receives rows
@@ -484,18 +485,7 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
   // transcript in front of the claims inside BLAKE3 chunk 0 (so that everything else of the claims digest is hashed early).
   const bool dev_outer = claim_words > 8192 && outer_fits(cap_digests, n_active) && pl_expected <= 1024 &&
                          blake3_num_chunks(pl_expected, claim_words) >= 2 && !getenv("MSAMD_HOST_TRANSCRIPT");
-  struct OuterDev {
-    DBuf<Digest> digest;
-    DBuf<u32> state;  // 12 words behind gamma, 8 words behind alpha
-    DBuf<E2> accs, alpha, points, tot;
-    DBuf<u32> lds;
-    DBuf<uint8_t> circuits;
-    std::vector<DBuf<uint8_t>> qdyn;  // per active circuit: QDyn, then the reversed alpha powers
-    Digest h_digest;
-    E2 h_bg[2], h_alpha;
-    std::vector<E2> h_points;
-    std::vector<unsigned> uniq_ld;  // the distinct trace heights: points[1 + k] = zeta * g(2^uniq_ld[k])
-  } od;
+  OuterDev od;
   LateChunk0 late0;
   if (sliced) {
     claims_cut(pl_expected, claim_words, n_claims, wit.claim_offsets.data(), N, me, sl_lo, sl_hi, inv_lo, inv_hi);
@@ -757,14 +747,8 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
     }
   }
   E2 beta = e2(0), gamma = e2(0), alpha = e2(0), zeta = e2(0);
-  auto tx_beta_gamma = [&]() {
-    beta = ch.sample_ext();
-    ch.observe_ext(beta);
-    gamma = ch.sample_ext();
-    ch.observe_ext(gamma);
-  };
   if (!dev_outer) {
-    tx_beta_gamma();
+    tx_beta_gamma(ch, beta, gamma);
     d_bg = challenge_bg_upload(ctx, beta, gamma);
   }
   // The claims accumulator (this rank's share of the fingerprints) and every circuit's logUp total stay in device memory:
@@ -846,7 +830,7 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
   }
   E2 acc_initial = e2(0);
   std::vector<E2> accs;
-  auto tx_alpha = [&]() {  // src/prover.rs:382-433; all_tot was delivered by a synchronisation since it was queued
+  auto host_alpha = [&]() {  // src/prover.rs:382-433; all_tot was delivered by a synchronisation since it was queued
     const std::vector<E2>& all = all_tot;
     acc_initial = e2(0);
     accs.clear();
@@ -858,9 +842,7 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
       acc = e2_add(acc, all[src * (NA + 1) + pos]);
       accs.push_back(acc);
     }
-    ch.observe_cap(s2.cap);
-    for (auto& a : accs) ch.observe_ext(a);
-    alpha = ch.sample_ext();
+    alpha = tx_alpha(ch, s2.cap, accs);
   };
   if (dev_outer) {
     // the same sums on the device, then alpha and every circuit's challenge block (outer_alpha_k)
@@ -887,7 +869,7 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
   } else {
     lap(2);
     tr.mark("stage2");
-    tx_alpha();
+    host_alpha();
   }
 
   // ---- quotient
@@ -906,29 +888,8 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
     m.w = 2 << log_q;
     m.owner = owners[ci];
     if (mine[pos]) {
-      QuotientArgs qa;
-      if (sys.has_pre && sys.pre_indices[ci] >= 0) {
-        const DMat& pm = sys.pre_data.ldes[sys.pre_indices[ci]];
-        qa.pre = pm.d();
-        qa.pre_h = pm.h;
-      }
-      qa.s1 = s1.mats[pos].full.d();
-      qa.s1_h = s1.mats[pos].h;
-      qa.s2 = s2.mats[pos].full.d();
-      qa.s2_h = s2.mats[pos].h;
-      qa.log_n = log_n;
-      qa.log_q = log_q;
-      if (dev_outer) {
-        qa.dyn = reinterpret_cast<const QDyn*>(od.qdyn[pos].p);
-        qa.alpha_rev = reinterpret_cast<const E2*>(od.qdyn[pos].p + sizeof(QDyn));
-      } else {
-        const E2 four[4] = {beta, gamma, pos == 0 ? acc_initial : accs[pos - 1], accs[pos]};
-        for (int k = 0; k < 4; k++) {
-          qa.publics[2 * k] = four[k].c0;
-          qa.publics[2 * k + 1] = four[k].c1;
-        }
-        qa.alpha = alpha;
-      }
+      QuotientArgs qa = fill_quotient_args(sys, ci, s1.mats[pos].full, s2.mats[pos].full, log_n, log_q, dev_outer ? od.qdyn[pos].p : nullptr);
+      if (!dev_outer) quotient_publics(qa, beta, gamma, pos ? accs[pos - 1] : acc_initial, accs[pos], alpha);
       DBuf<u64> qv(ctx, nq * 2);
       quotient_eval(ctx, c.prog, qa, qv.p);
       m.full.h = m.h;
@@ -939,32 +900,11 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
     qd.mats.push_back(std::move(m));
   }
   sharded_commit(cm, qd, (unsigned)prm.cap_height, nullptr, nullptr, dev_outer);
-  auto tx_zeta = [&]() {
-    ch.observe_cap(qd.cap);
-    zeta = ch.sample_ext();
-  };
   // zeta and zeta * g per trace height: values in host mode, placeholders for device values otherwise (swapped for the values
   // when the opened-value sums have arrived and the host has replayed the transcript)
   E2 pt_zeta = e2(0);
   std::vector<E2> pt_next(NA);
-  if (dev_outer) {
-    std::vector<size_t> id_of(NA);
-    for (size_t pos = 0; pos < NA; pos++) {
-      size_t k = 0;
-      while (k < od.uniq_ld.size() && od.uniq_ld[k] != log_degrees[pos]) k++;
-      if (k == od.uniq_ld.size()) od.uniq_ld.push_back(log_degrees[pos]);
-      id_of[pos] = 1 + k;
-    }
-    const size_t n_ld = od.uniq_ld.size();
-    od.lds = DBuf<u32>(ctx, n_ld);
-    ctx.h2d(od.lds.p, od.uniq_ld.data(), n_ld * sizeof(u32));
-    od.points = DBuf<E2>(ctx, 1 + n_ld);
-    od.h_points.assign(1 + n_ld, e2(0));
-    outer_zeta(ctx, od.state.p + 12, qd.d_cap, cap_digests, od.lds.p, n_ld, od.points.p);
-    ctx.d2h_queue(od.h_points.data(), od.points.p, (1 + n_ld) * sizeof(E2));
-    pt_zeta = sym_point(0);
-    for (size_t pos = 0; pos < NA; pos++) pt_next[pos] = sym_point(id_of[pos]);
-  }
+  if (dev_outer) zeta_placeholders(ctx, od, log_degrees, qd.d_cap, cap_digests, nullptr, pt_zeta, pt_next);
   lap(3);
   tr.mark("quotient");
 
@@ -972,12 +912,12 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
   t0 = now_ms();
   cm.phase = "opening";
   if (!dev_outer) {
-    tx_zeta();
+    zeta = tx_zeta(ch, qd.cap);
     pt_zeta = zeta;
     for (size_t pos = 0; pos < NA; pos++) pt_next[pos] = e2_mul_base(zeta, gl_two_adic_generator(log_degrees[pos]));
   }
   ShardedCommit* scs[3] = {&s1, &s2, &qd};
-  // points per round / matrix, as in the single-GPU prover: rounds 0..2 = s1, s2, quotient; round 3 = preprocessed
+  // points per round / matrix: rounds 0..2 = s1, s2, quotient; round 3 = preprocessed
   std::vector<std::vector<std::vector<E2>>> rpoints(3);
   for (size_t pos = 0; pos < NA; pos++) {
     rpoints[0].push_back({pt_zeta, pt_next[pos]});
@@ -1017,29 +957,21 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
       gw = std::max(gw, m.w);
     }
   const unsigned log_gmax = log2_strict(gmax);
-  std::vector<E2> upts;
-  std::vector<size_t> uh;
-  auto point_index = [&](E2 z) -> size_t {
-    for (size_t i = 0; i < upts.size(); i++)
-      if (e2_same(upts[i], z)) return i;
-    upts.push_back(z);
-    uh.push_back(0);
-    return upts.size() - 1;
-  };
+  OpenPoints op;
   for (int ri = 0; ri < 3; ri++)
     for (size_t mi = 0; mi < NA; mi++)
       for (size_t pi = 0; pi < rpoints[ri][mi].size(); pi++) {
         if (pi == 1 && is_next(rpoints[ri][mi])) continue;  // read through the first point's arrays
-        size_t k = point_index(rpoints[ri][mi][pi]);
-        uh[k] = std::max(uh[k], scs[ri]->mats[mi].h);
+        op.note(rpoints[ri][mi][pi], scs[ri]->mats[mi].h);
       }
   if (sys.has_pre)
     for (size_t mi = 0; mi < sys.pre_data.ldes.size(); mi++)
       for (size_t pi = 0; pi < pre_points[mi].size(); pi++) {
         if (pi == 1 && is_next(pre_points[mi])) continue;
-        size_t k = point_index(pre_points[mi][pi]);
-        uh[k] = std::max(uh[k], sys.pre_data.ldes[mi].h);
+        op.note(pre_points[mi][pi], sys.pre_data.ldes[mi].h);
       }
+  const std::vector<E2>& upts = op.upts;
+  const std::vector<size_t>& uh = op.uh;
   // short matrices beside tall ones: their launches go to the side stream, queued behind the tall ones'
   const size_t short_h = size_t(1) << (ctx.side_max_log + lb);
   const bool open_side = use_side && gmax > short_h;
@@ -1130,8 +1062,8 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
       const std::vector<E2>& pts = e.ri < 3 ? rpoints[e.ri][e.mi] : pre_points[e.mi];
       const int np = (int)pts.size();
       const bool nx = is_next(pts);
-      const E2* d0 = xdens[point_index(pts[0])].p;
-      const E2* d1 = np == 2 && !nx ? xdens[point_index(pts[1])].p : d0;
+      const E2* d0 = xdens[op.index(pts[0])].p;
+      const E2* d1 = np == 2 && !nx ? xdens[op.index(pts[1])].p : d0;
       specs.push_back(BarySpec{m.d(), m.h, m.w, log2_strict(m.h) - lb, d0, d1, np, d_sums.p + e.off, nx});
     }
     if (!specs.empty()) {
@@ -1183,26 +1115,14 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
     s2.finish();
     qd.finish();
     ch.flush_with(od.h_digest);
-    tx_beta_gamma();
-    tx_alpha();
-    tx_zeta();
-    bool same = e2_same(beta, od.h_bg[0]) && e2_same(gamma, od.h_bg[1]) && e2_same(alpha, od.h_alpha) && e2_same(zeta, od.h_points[0]);
-    std::vector<E2> values(1 + od.uniq_ld.size());
-    values[0] = zeta;
-    for (size_t k = 0; k < od.uniq_ld.size(); k++) {
-      values[1 + k] = e2_mul_base(zeta, gl_two_adic_generator(od.uniq_ld[k]));
-      same = same && e2_same(values[1 + k], od.h_points[1 + k]);
-    }
-    if (!same) throw std::runtime_error("the device transcript's challenges differ from the host challenger's");
-    auto swap_in = [&](E2& z) {
-      if (is_sym_point(z)) z = values[z.c0];
-    };
-    for (auto& z : upts) swap_in(z);
+    tx_beta_gamma(ch, beta, gamma);
+    host_alpha();
+    zeta = tx_zeta(ch, qd.cap);
+    const std::vector<E2> values = replayed_points(od, beta, gamma, alpha, zeta);
+    op.resolve(values);
     for (auto& r : rpoints)
-      for (auto& pts : r)
-        for (auto& z : pts) swap_in(z);
-    for (auto& pts : pre_points)
-      for (auto& z : pts) swap_in(z);
+      for (auto& pts : r) swap_in(pts, values);
+    for (auto& pts : pre_points) swap_in(pts, values);
   }
   std::vector<OpenedRound> opened(sys.has_pre ? 4 : 3);
   for (int ri = 0; ri < 3; ri++) opened[ri].resize(NA);
@@ -1210,10 +1130,7 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
   for (auto& e : evs) {
     const DMat& m = e.ri < 3 ? scs[e.ri]->mats[e.mi].full : sys.pre_data.ldes[e.mi];
     const std::vector<E2>& pts = e.ri < 3 ? rpoints[e.ri][e.mi] : pre_points[e.mi];
-    const int np = (int)pts.size();
-    std::vector<E2> ys(np * m.w);
-    bary_finish(&h_sums[e.off], m.w, log2_strict(m.h) - lb, pts.data(), np, ys.data());
-    for (int p = 0; p < np; p++) opened[e.ri][e.mi].emplace_back(ys.begin() + p * m.w, ys.begin() + (p + 1) * m.w);
+    opened[e.ri][e.mi] = finish_opened(&h_sums[e.off], m.w, log2_strict(m.h) - lb, pts);
   }
   {
     std::vector<size_t> cursor(N, 0);  // position inside each rank's blob
@@ -1228,89 +1145,46 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& wit, const ms_comm_t*
       for (int ri = 0; ri < 3; ri++) {
         const ShardMat& m = scs[ri]->mats[pos];
         const std::vector<E2>& pts = rpoints[ri][pos];
-        const int np = (int)pts.size();
-        std::vector<E2> ys(np * m.w);
-        bary_finish(src + off, m.w, log2_strict(m.h) - lb, pts.data(), np, ys.data());
-        for (int p = 0; p < np; p++) opened[ri][pos].emplace_back(ys.begin() + p * m.w, ys.begin() + (p + 1) * m.w);
-        off += np * m.w;
+        opened[ri][pos] = finish_opened(src + off, m.w, log2_strict(m.h) - lb, pts);
+        off += pts.size() * m.w;
       }
     }
   }
-  // observe in round -> matrix -> point order; rounds as the single-GPU prover orders them: s1, s2, quotient, pre
+  // observe in round -> matrix -> point order; rounds as prove() orders them: s1, s2, quotient, pre
   for (auto& orr : opened)
     for (auto& m : orr)
       for (auto& pt : m)
         for (auto& y : pt) ch.observe_ext(y);
   tr.mark("opened_values");
   const E2 alpha_fri = ch.sample_ext();
-  std::vector<E2> apow(gw + 1);
-  apow[0] = e2(1);
-  for (size_t i = 1; i <= gw; i++) apow[i] = e2_mul(apow[i - 1], alpha_fri);
+  const std::vector<E2> apow = alpha_powers(alpha_fri, gw);
   DBuf<E2> d_apow(ctx, gw + 1);
   ctx.h2d(d_apow.p, apow.data(), (gw + 1) * sizeof(E2));
 
   // ---- reduced openings per LDE height: heights with sharded matrices on this rank's row range (then all-gathered),
   // the others replicated
-  std::vector<size_t> num_reduced(33, 0);
-  std::vector<std::vector<DeepMat>> lists(33);
-  std::vector<DeepPoints> hpts(33);
-  std::vector<std::vector<size_t>> hpt_global(33);
-  std::vector<char> present(33, 0), sharded_h(33, 0);
-  constexpr size_t NEXT_MARK = size_t(1) << 62;
-  for (auto& hp : hpts) memset(&hp, 0, sizeof(hp));
+  std::vector<char> sharded_h(33, 0);
   for (int ri = 0; ri < 3; ri++)
     for (auto& m : scs[ri]->mats)
       if (m.owner >= 0) sharded_h[log2_strict(m.h)] = 1;
-  auto add_deep = [&](int ri, size_t mi, size_t h, size_t w, const u64* full, const u64* slice, size_t slice_stride, const std::vector<E2>& pts) {
-    const unsigned lh = log2_strict(h);
-    present[lh] = 1;
-    if (pts.empty()) return;
-    DeepMat dm;
-    memset(&dm, 0, sizeof(dm));
-    // at a sharded height every matrix is read through its local row range (column stride = rows of the range)
-    dm.d = sharded_h[lh] ? slice : full;
-    dm.stride = sharded_h[lh] ? slice_stride : 0;
-    dm.w = (uint32_t)w;
-    dm.npoints = (uint32_t)pts.size();
-    const bool nxm = is_next(pts);
-    for (size_t pi = 0; pi < pts.size(); pi++) {
-      // a "next" point is named by the first point's arrays plus a mark (all matrices of one height share g)
-      const bool nx = pi == 1 && nxm;
-      const size_t gk = point_index(pts[nx ? 0 : pi]) | (nx ? NEXT_MARK : size_t(0));
-      size_t local = 0;
-      while (local < hpt_global[lh].size() && hpt_global[lh][local] != gk) local++;
-      if (local == hpt_global[lh].size()) {
-        if (local == 2) throw std::runtime_error("pcs_open: more than two opening points at one LDE height");
-        hpt_global[lh].push_back(gk);
-        hpts[lh].den[local] = dens[gk & ~NEXT_MARK].p;  // indexed by the full domain's row (deep_reduce's row0)
-        hpts[lh].shift[local] = nx ? (uint32_t(1) << lb) : 0u;  // g = w_H^blowup
-        hpts[lh].K[local] = e2(0);
-        hpts[lh].n = (uint32_t)(local + 1);
-      }
-      E2 coeff = e2_pow(alpha_fri, num_reduced[lh]);
-      E2 rz = e2(0);
-      const std::vector<E2>& ys = opened[ri][mi][pi];
-      for (size_t c = 0; c < w; c++) rz = e2_add(rz, e2_mul(apow[c], ys[c]));
-      if (nx) coeff = e2_mul_base(coeff, gl_inv(gl_two_adic_generator(lh - lb)));  // 1 / (z g - x_j) = g^-1 / (z - x_sigma(j))
-      dm.pt[pi] = (uint32_t)local;
-      dm.coeff[pi] = coeff;
-      dm.coeff7[pi] = gl_mul(coeff.c1, GL_EXT_W);
-      hpts[lh].K[local] = e2_add(hpts[lh].K[local], e2_mul(coeff, rz));
-      num_reduced[lh] += w;
-    }
-    lists[lh].push_back(dm);
-  };
+  DeepPlan plan(op, dens, alpha_fri, apow, lb);
   for (int ri = 0; ri < 3; ri++)
     for (size_t mi = 0; mi < NA; mi++) {
       const ShardMat& m = scs[ri]->mats[mi];
-      add_deep(ri, mi, m.h, m.w, m.full.d(), m.slice, m.slice_stride, rpoints[ri][mi]);
+      const unsigned lh = log2_strict(m.h);
+      // at a sharded height every matrix is read through its local row range (column stride = rows of the range)
+      plan.add(lh, sharded_h[lh] ? m.slice : m.full.d(), sharded_h[lh] ? m.slice_stride : 0, m.w, rpoints[ri][mi], is_next(rpoints[ri][mi]), opened[ri][mi]);
     }
   if (sys.has_pre)
     for (size_t mi = 0; mi < sys.pre_data.ldes.size(); mi++) {
       const DMat& m = sys.pre_data.ldes[mi];
+      const unsigned lh = log2_strict(m.h);
       // (a preprocessed matrix that shares a sharded height is read through its row range in place)
-      add_deep(3, mi, m.h, m.w, m.d(), m.d() + me * (m.h / N), m.h, pre_points[mi]);
+      plan.add(lh, sharded_h[lh] ? m.d() + me * (m.h / N) : m.d(), sharded_h[lh] ? m.h : 0, m.w, pre_points[mi], is_next(pre_points[mi]), opened[3][mi]);
     }
+  const auto& lists = plan.lists;
+  const auto& hpts = plan.hpts;
+  const auto& present = plan.present;
   // Row-sharded FRI head (SURVEY 8e item 5): when the tallest reduced-opening vector is the (only) sharded one, its first
   // log2 N commit-phase rounds run on the ranks' row ranges - contiguous storage rows are closed under the fold's pairs and
   // form a sub-tree of each round's Merkle tree - with one all-gather of N sub-tree roots per round; only the remainder
