@@ -62,6 +62,14 @@ pub struct ms_comm {
     pub abort: Option<unsafe extern "C" fn(user: *mut c_void, why: *const c_char)>,
 }
 pub const MS_COMM_SKIP_SELF: u32 = 1;
+/// `flags` of ms_system_circuit_kernels / msbb_system_circuit_kernels: the circuit's kernels that were generated and compiled
+pub const MS_KERNEL_QUOTIENT: u32 = 0x1;
+pub const MS_KERNEL_QUOTIENT_INLINE: u32 = 0x2;
+pub const MS_KERNEL_STAGE2: u32 = 0x4;
+pub const MS_KERNEL_STAGE2_GROUPED: u32 = 0x8;
+pub const MS_KERNEL_STAGE2_TRACE: u32 = 0x10;
+pub const MS_KERNEL_STAGE2_GROUPS_SHIFT: u32 = 8;
+pub const MS_KERNEL_STAGE2_GROUPS_MASK: u32 = 0x1f;
 
 extern "C" {
     // ---- include/mstark.h (GoldilocksBlake3Config)
@@ -83,6 +91,7 @@ extern "C" {
     pub fn ms_system_destroy(sys: *mut ms_system);
     pub fn ms_system_preprocessed_commit(sys: *const ms_system, out: *mut u8, cap: usize, n_digests: *mut usize) -> i32;
     pub fn ms_system_circuit_info(sys: *const ms_system, circuit: usize, out9: *mut u64) -> i32;
+    pub fn ms_system_circuit_kernels(sys: *const ms_system, circuit: usize, flags: *mut u32) -> i32;
     pub fn ms_witness_create(sys: *mut ms_system, traces: *const *const u64, heights: *const u64, mult: *const *const u64,
                              args: *const *const u64, n_claims: usize, claim_offsets: *const u64, claim_data: *const u64,
                              out: *mut *mut ms_witness) -> i32;
@@ -165,6 +174,7 @@ extern "C" {
     pub fn msbb_system_destroy(sys: *mut msbb_system);
     pub fn msbb_system_preprocessed_commit(sys: *const msbb_system, out: *mut u32, cap_words: usize, n_digests: *mut usize) -> i32;
     pub fn msbb_system_circuit_info(sys: *const msbb_system, circuit: usize, out9: *mut u64) -> i32;
+    pub fn msbb_system_circuit_kernels(sys: *const msbb_system, circuit: usize, flags: *mut u32) -> i32;
     pub fn msbb_witness_create(sys: *mut msbb_system, traces: *const *const u32, heights: *const u64, n_claims: usize,
                                claim_offsets: *const u64, claim_data: *const u32, out: *mut *mut msbb_witness) -> i32;
     pub fn msbb_witness_create_host(sys: *mut msbb_system, traces: *const *const u32, heights: *const u64, n_claims: usize,

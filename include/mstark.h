@@ -98,6 +98,18 @@ int32_t ms_system_preprocessed_commit(const ms_system* sys, uint8_t* out, size_t
 /* [main_width, pre_width, pre_height, num_lookups, stage2_width, constraint_count, max_constraint_degree,
  *  quotient_degree, args_width] */
 int32_t ms_system_circuit_info(const ms_system* sys, size_t circuit, uint64_t out9[9]);
+/* Diagnostics: which of the circuit's kernels were generated and compiled at ms_system_create (hiprtc; a circuit without
+ * one runs the generic interpreter kernels and produces the same bytes). *flags = a mask of MS_KERNEL_*; 0 when nothing was
+ * compiled (no hiprtc, MSAMD_NO_JIT=1, a program over the size limits). The group count G of a grouped stage-2 terms
+ * kernel (one wave per 16 lookups) is (*flags >> MS_KERNEL_STAGE2_GROUPS_SHIFT) & MS_KERNEL_STAGE2_GROUPS_MASK. */
+#define MS_KERNEL_QUOTIENT 0x1u         /* quotient kernel compiled */
+#define MS_KERNEL_QUOTIENT_INLINE 0x2u  /* ... and it reads the Z_H tables from the argument block */
+#define MS_KERNEL_STAGE2 0x4u           /* stage-2 terms kernel (fed by lookup values) compiled */
+#define MS_KERNEL_STAGE2_GROUPED 0x8u   /* ... in grouped form: G waves per 64 rows */
+#define MS_KERNEL_STAGE2_TRACE 0x10u    /* stage-2 terms kernel fed by the trace (host-resident witnesses) compiled */
+#define MS_KERNEL_STAGE2_GROUPS_SHIFT 8
+#define MS_KERNEL_STAGE2_GROUPS_MASK 0x1fu
+int32_t ms_system_circuit_kernels(const ms_system* sys, size_t circuit, uint32_t* flags);
 
 /* ---- SystemWitness (src/system.rs:225-233) + claims. traces[i]: heights[i] x main_width_i row-major (height 0 =
  * inactive circuit). mult[i] / args[i]: the flat LookupValues storage (src/lookup.rs:392-405); pass mult = NULL

@@ -38,6 +38,8 @@ void msbb_system_destroy(msbb_system* sys);
 int32_t msbb_system_preprocessed_commit(const msbb_system* sys, uint32_t* out, size_t cap_words, size_t* n_digests);
 /* the nine numbers of ms_system_circuit_info */
 int32_t msbb_system_circuit_info(const msbb_system* sys, size_t circuit, uint64_t out9[9]);
+/* as ms_system_circuit_kernels; this configuration generates the quotient kernel only: *flags = MS_KERNEL_QUOTIENT or 0 */
+int32_t msbb_system_circuit_kernels(const msbb_system* sys, size_t circuit, uint32_t* flags);
 
 /* traces[i]: heights[i] x main_width_i row-major canonical u32 (height 0 = inactive circuit). The lookup values of
  * SystemWitness::from_stage_1 (src/system.rs:244-328) are computed on the device. Claims: offsets (n_claims + 1) into

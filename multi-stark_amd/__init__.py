@@ -43,7 +43,7 @@ def exported_symbols():
     """Every entry point include/mstark.h declares (used by the CPU-side ABI test)."""
     return ["ms_last_error", "ms_device_count", "ms_ctx_create", "ms_ctx_destroy", "ms_ctx_sync", "ms_ctx_sync_count", "ms_ctx_trim", "ms_ctx_set_profile_mask",
             "ms_ctx_kernel_stats", "ms_ctx_kernel_units", "ms_ctx_reset_stats", "ms_ctx_debug_fail_alloc", "ms_kernel_count", "ms_kernel_name", "ms_system_create",
-            "ms_system_destroy", "ms_system_preprocessed_commit", "ms_system_circuit_info", "ms_witness_create", "ms_witness_create_host", "ms_claims_slice_range", "ms_witness_create_host_sliced", "ms_witness_prefetch",
+            "ms_system_destroy", "ms_system_preprocessed_commit", "ms_system_circuit_info", "ms_system_circuit_kernels", "ms_witness_create", "ms_witness_create_host", "ms_claims_slice_range", "ms_witness_create_host_sliced", "ms_witness_prefetch",
             "ms_witness_u32_add_bench", "ms_witness_destroy", "ms_prove", "ms_prove_sharded", "ms_ctx_comm_progress", "ms_comm_rccl_unique_id", "ms_comm_rccl_create",
             "ms_comm_rccl_table", "ms_comm_rccl_bytes_moved", "ms_comm_rccl_destroy", "ms_comm_local_group_create", "ms_comm_local_group_abort",
             "ms_comm_local_group_destroy", "ms_comm_local_create", "ms_comm_local_table", "ms_comm_local_bytes_moved", "ms_comm_local_destroy", "ms_verify", "ms_dft_batch", "ms_coset_lde_batch", "ms_quotient_lde", "ms_mmcs_commit",
@@ -53,6 +53,15 @@ def exported_symbols():
             "ms_quotient_values", "ms_field_op", "ms_trace_destroy", "ms_trace_info", "ms_system_preprocessed_mmcs",
             "ms_witness_commit_stage1", "ms_challenger_observe_claims", "ms_witness_claims_accumulator", "ms_stage2_build",
             "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes"]
+
+
+# ms_system_circuit_kernels / msbb_system_circuit_kernels (MS_KERNEL_* in include/mstark.h)
+KERNEL_QUOTIENT, KERNEL_QUOTIENT_INLINE, KERNEL_STAGE2, KERNEL_STAGE2_GROUPED, KERNEL_STAGE2_TRACE = 0x1, 0x2, 0x4, 0x8, 0x10
+
+
+def kernel_groups(flags):
+    """G of a grouped stage-2 terms kernel (0 when it is not grouped)"""
+    return (flags >> 8) & 0x1F
 
 
 def _check(rc):
@@ -471,6 +480,13 @@ class System:
         keys = ["main_width", "pre_width", "pre_height", "num_lookups", "stage2_width", "constraint_count",
                 "max_constraint_degree", "quotient_degree", "args_width"]
         return dict(zip(keys, (int(x) for x in o)))
+
+    def circuit_kernels(self, ci):
+        """ms_system_circuit_kernels: the mask of KERNEL_* bits of the kernels generated and compiled for circuit `ci` (0 = the
+        generic interpreter kernels do all its work); the group count of a grouped stage-2 kernel is kernel_groups(flags)"""
+        f = C.c_uint32()
+        _check(lib().ms_system_circuit_kernels(self.h, C.c_size_t(ci), C.byref(f)))
+        return int(f.value)
 
     def witness(self, traces, claims_packed, lookups=None, remote_heights=None):
         """`SystemWitness::from_stage_1` (lookups=None) or an explicit SystemWitness{traces, lookups}; uploads to HBM.

@@ -17,7 +17,7 @@ P = frontend.BABYBEAR["P"]
 
 def exported_symbols():
     """Every entry point include/mstark_bb.h declares (used by the CPU-side ABI test)."""
-    return ["msbb_system_create", "msbb_system_destroy", "msbb_system_preprocessed_commit", "msbb_system_circuit_info",
+    return ["msbb_system_create", "msbb_system_destroy", "msbb_system_preprocessed_commit", "msbb_system_circuit_info", "msbb_system_circuit_kernels",
             "msbb_witness_create", "msbb_witness_create_host", "msbb_witness_destroy", "msbb_prove", "msbb_verify", "msbb_set_poseidon2", "msbb_poseidon2_permute",
             "msbb_dft_batch", "msbb_coset_lde_batch", "msbb_mmcs_commit", "msbb_mmcs_open", "msbb_mmcs_destroy", "msbb_field_op",
             "msbb_challenger_create", "msbb_challenger_destroy", "msbb_challenger_observe", "msbb_challenger_observe_digests",
@@ -118,6 +118,12 @@ class System:
         keys = ["main_width", "pre_width", "pre_height", "num_lookups", "stage2_width", "constraint_count", "max_constraint_degree",
                 "quotient_degree", "args_width"]
         return dict(zip(keys, (int(x) for x in o)))
+
+    def circuit_kernels(self, ci):
+        """msbb_system_circuit_kernels: KERNEL_QUOTIENT when the circuit's quotient kernel was generated and compiled, else 0"""
+        f = C.c_uint32()
+        _check(_lib().msbb_system_circuit_kernels(self.h, C.c_size_t(ci), C.byref(f)))
+        return int(f.value)
 
     def preprocessed_commit(self):
         out = np.zeros(8 * 256, dtype=np.uint32)

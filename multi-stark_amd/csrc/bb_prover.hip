@@ -1796,6 +1796,14 @@ int32_t msbb_system_circuit_info(const msbb_system* sys, size_t circuit, uint64_
   return MS_OK;
   BB_CATCH
 }
+int32_t msbb_system_circuit_kernels(const msbb_system* sys, size_t circuit, uint32_t* flags) {
+  BB_TRY
+  if (!sys || !flags) throw std::runtime_error("null argument");
+  if (circuit >= sys->sys->circuits.size()) throw std::runtime_error("circuit index out of range");
+  *flags = sys->sys->circuits[circuit].quotient_jit.function ? MS_KERNEL_QUOTIENT : 0u;
+  return MS_OK;
+  BB_CATCH
+}
 int32_t msbb_witness_create(msbb_system* sys, const uint32_t* const* traces, const uint64_t* heights, size_t n_claims,
                             const uint64_t* claim_offsets, const uint32_t* claim_data, msbb_witness** out) {
   BB_TRY

@@ -217,6 +217,22 @@ int32_t ms_system_circuit_info(const ms_system* sys, size_t ci, uint64_t out9[9]
   return MS_OK;
   MS_CATCH
 }
+int32_t ms_system_circuit_kernels(const ms_system* sys, size_t ci, uint32_t* flags) {
+  MS_TRY if (!sys || !flags) throw std::runtime_error("null argument");
+  const HSystem& s = *sys->sys;
+  if (ci >= s.circuits.size()) throw std::runtime_error("circuit index out of range");
+  const HCircuit& c = s.circuits[ci];
+  uint32_t f = 0;
+  if (c.prog.jit.function) f |= MS_KERNEL_QUOTIENT | (c.prog.jit.inline_tables ? MS_KERNEL_QUOTIENT_INLINE : 0u);
+  if (c.stage2_jit.function) {
+    f |= MS_KERNEL_STAGE2;
+    if (c.stage2_jit.groups) f |= MS_KERNEL_STAGE2_GROUPED | ((c.stage2_jit.groups & MS_KERNEL_STAGE2_GROUPS_MASK) << MS_KERNEL_STAGE2_GROUPS_SHIFT);
+  }
+  if (c.stage2_trace_jit.function) f |= MS_KERNEL_STAGE2_TRACE;
+  *flags = f;
+  return MS_OK;
+  MS_CATCH
+}
 
 int32_t ms_witness_create(ms_system* sys, const uint64_t* const* traces, const uint64_t* heights, const uint64_t* const* mult,
                           const uint64_t* const* args, size_t n_claims, const uint64_t* claim_offsets,

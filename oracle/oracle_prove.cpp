@@ -162,6 +162,11 @@ Witness witness_from_stage_1(const System& sys, std::vector<Mat>&& traces) {
     lv.mult.assign(tr.h * lv.num_lookups, 0);
     lv.args.assign(tr.h * aw, 0);
     size_t plen = lookup_prefix_len(c);
+    // there are no publics and no stage-2 trace at witness time (src/system.rs:311 hands the sweep an empty slice: the
+    // reference panics on the index)
+    for (size_t i = 0; i < plen; i++)
+      if (c.nodes[i].kind == N_PUBLIC || (c.nodes[i].kind == N_VAR && c.nodes[i].source == SRC_STAGE2))
+        throw std::runtime_error("public input or stage-2 column in a lookup expression");
 #pragma omp parallel
     {
       std::vector<u64> buf;

@@ -16,6 +16,7 @@ usage: python3 tools/fuzz_parity.py [N_CASES] [SEED]      (MSAMD_NO_JIT=1 skips 
        FUZZ_FIELD=babybear python3 tools/fuzz_parity.py ...   the same systems over the reference's second configuration
        (BabyBear / Poseidon2, include/mstark_bb.h) against oracle/libms_oracle_bb.so
 The oracle is used only as the checker."""
+import contextlib
 import os
 import sys
 import time
@@ -34,26 +35,29 @@ BIG = bool(os.environ.get("FUZZ_BIG"))  # wider / taller systems: rows over one 
 LONG_CLAIMS = bool(os.environ.get("FUZZ_CLAIMS"))  # more than 8192 claim words: the claims digest and the outer transcript run on the device
 
 
-def rand_field(rng, shape):
-    v = rng.integers(0, P, shape, dtype=np.uint64)
-    edge = np.array([0, 1, 2, P - 1, P - 2, (1 << 32) - 1, 1 << 32, (1 << 32) + 1], dtype=np.uint64) % np.uint64(P)
+def rand_field(rng, shape, p=None):
+    """p: the field's modulus (default: the one FUZZ_FIELD chose)"""
+    p = P if p is None else p
+    v = rng.integers(0, p, shape, dtype=np.uint64)
+    edge = np.array([0, 1, 2, p - 1, p - 2, (1 << 32) - 1, 1 << 32, (1 << 32) + 1], dtype=np.uint64) % np.uint64(p)
     mask = rng.random(shape) < 0.15
     return np.where(mask, edge[rng.integers(0, len(edge), shape)], v)
 
 
-def random_expr(rng, fe, atoms, depth, max_degree):
+def random_expr(rng, fe, atoms, depth, max_degree, p=None):
     """(expr, degree) with degree <= max_degree"""
     E = fe.Expr
+    p = P if p is None else p
     if depth == 0 or rng.random() < 0.25:
         k = rng.integers(0, len(atoms) + 1)
         if k == len(atoms):
-            return E.const(int(rng.integers(0, P, dtype=np.uint64))), 0
+            return E.const(int(rng.integers(0, p, dtype=np.uint64))), 0
         return atoms[k], 1
     op = rng.integers(0, 4)
-    a, da = random_expr(rng, fe, atoms, depth - 1, max_degree)
+    a, da = random_expr(rng, fe, atoms, depth - 1, max_degree, p)
     if op == 3:
         return -a, da
-    b, db = random_expr(rng, fe, atoms, depth - 1, max_degree)
+    b, db = random_expr(rng, fe, atoms, depth - 1, max_degree, p)
     if op == 2:
         if da + db <= max_degree:
             return a * b, da + db
@@ -61,19 +65,19 @@ def random_expr(rng, fe, atoms, depth, max_degree):
     return (a + b, max(da, db)) if op == 0 else (a - b, max(da, db))
 
 
-def random_circuit(rng, fe, log_blowup):
+def random_circuit(rng, fe, log_blowup, p=None):
     E = fe.Expr
     w = int(rng.integers(1, 150 if BIG and rng.random() < 0.3 else 7))
     pw = int(rng.integers(0, 4)) if rng.random() < 0.4 else 0
     h = 1 << int(rng.integers(0, 16 if BIG else 11))
-    pre = rand_field(rng, (h, pw)) if pw else None
+    pre = rand_field(rng, (h, pw), p) if pw else None
     atoms = [E.main(i) for i in range(w)] + [E.main_next(i) for i in range(w)]
     atoms += [E.var(fe.SRC_PRE, 0, i) for i in range(pw)] + [E.var(fe.SRC_PRE, 1, i) for i in range(pw)]
     max_deg = min(3, (1 << log_blowup) + 1)
 
     def ev(b):
         for _ in range(int(rng.integers(0, 4))):
-            e, _d = random_expr(rng, fe, atoms, 3, max_deg - (1 if rng.random() < 0.3 else 0))
+            e, _d = random_expr(rng, fe, atoms, 3, max_deg - (1 if rng.random() < 0.3 else 0), p)
             r = rng.random()
             if r < 0.2:
                 b.when_transition().assert_zero(e) if _d < max_deg else b.assert_zero(e)
@@ -88,13 +92,19 @@ def random_circuit(rng, fe, log_blowup):
     latoms = [E.main(i) for i in range(w)] + [E.var(fe.SRC_PRE, 0, i) for i in range(pw)]
     lookups = []
     for _ in range(int(rng.integers(0, 40 if BIG and rng.random() < 0.3 else 5))):
-        m, _ = random_expr(rng, fe, latoms, 1, 1)
-        args = [random_expr(rng, fe, latoms, 2, 2)[0] for _ in range(int(rng.integers(0, 70 if BIG and rng.random() < 0.1 else 6)))]
+        m, _ = random_expr(rng, fe, latoms, 1, 1, p)
+        args = [random_expr(rng, fe, latoms, 2, 2, p)[0] for _ in range(int(rng.integers(0, 70 if BIG and rng.random() < 0.1 else 6)))]
         lookups.append(fe.Lookup.push(m, args) if rng.random() < 0.5 else fe.Lookup.pull(m, args))
     return fe.lookup_air(w, ev, lookups, pre), w, h if pw else None
 
 
-def one_case(pkg, fe, oracle, ctx, rng, case):
+def one_case(pkg, fe, oracle, ctx, rng, case, on_system=None, babybear=None, kperm=None):
+    """on_system: called with the library's System once it exists (e.g. to read circuit_kernels). babybear / kperm: the field
+    and, for BabyBear, the Poseidon2 constants (default: what FUZZ_FIELD chose; the caller authors under fe.field(...) and
+    passes the matching oracle)"""
+    babybear = BABYBEAR if babybear is None else babybear
+    kperm = KPERM if kperm is None else kperm
+    p = fe.P  # the caller authors under fe.field(...): the front end's modulus is the case's
     lb = int(rng.integers(1, 4))
     # FUZZ_ARITY=1: FRI rounds of arity up to 2^6 (drawn from the case number, so the rest of the case is the same system)
     mla = 1 + int(np.random.default_rng(1000 + int(case)).integers(0, 6)) if os.environ.get("FUZZ_ARITY") else 1
@@ -110,30 +120,30 @@ def one_case(pkg, fe, oracle, ctx, rng, case):
     # FUZZ_MANY=1: systems of 4 .. 40 circuits (many trace heights, many FRI inputs, long matrix lists) instead of 1 .. 3
     n_circuits = int(np.random.default_rng(2000 + int(case)).integers(4, 41)) if os.environ.get("FUZZ_MANY") else int(rng.integers(1, 4))
     for _ in range(n_circuits):
-        ci, w, fixed_h = random_circuit(rng, fe, lb)
+        ci, w, fixed_h = random_circuit(rng, fe, lb, p)
         circuits.append(ci)
         h = fixed_h if fixed_h else 1 << int(rng.integers(0, 16 if BIG else 11))
         if rng.random() < 0.12:
             h = 0  # inactive circuit
-        traces.append(rand_field(rng, (h, w)))
+        traces.append(rand_field(rng, (h, w), p))
     if all(t.shape[0] == 0 for t in traces):
-        traces[0] = rand_field(rng, (circuits[0].preprocessed.shape[0] if circuits[0].preprocessed is not None else 4, traces[0].shape[1]))
-    claims = [[int(x) for x in rand_field(rng, int(rng.integers(0, 6)))] for _ in range(int(rng.integers(0, 5)))]
-    if LONG_CLAIMS and not BABYBEAR:
+        traces[0] = rand_field(rng, (circuits[0].preprocessed.shape[0] if circuits[0].preprocessed is not None else 4, traces[0].shape[1]), p)
+    claims = [[int(x) for x in rand_field(rng, int(rng.integers(0, 6)), p)] for _ in range(int(rng.integers(0, 5)))]
+    if LONG_CLAIMS and not babybear:
         # few long claims or many short ones, 8200 .. 20000 words in all (csrc/outer.hip takes over above 8192)
         n_cl = int(rng.choice([1, 2, 7, 100, 255, 256, 257, 700, 3000]))
         total = int(rng.integers(8200, 20000))
         cuts = np.sort(rng.integers(0, total + 1, n_cl - 1)) if n_cl > 1 else np.array([], dtype=np.int64)
         lens = np.diff(np.concatenate([[0], cuts, [total]]))
-        claims = [[int(x) for x in rand_field(rng, int(m))] for m in lens]
+        claims = [[int(x) for x in rand_field(rng, int(m), p)] for m in lens]
     packed = fe.pack_claims(claims)
     try:
         compiled = [fe.compile_circuit(c) for c in circuits]
     except fe.CompileError:
         return "front-end-rejected"  # e.g. a constraint that folded to a non-zero constant (src/graph.rs)
-    blob = fe.system_blob(params, compiled, KPERM) if BABYBEAR else fe.system_blob(params, compiled)
+    blob = fe.system_blob(params, compiled, kperm) if babybear else fe.system_blob(params, compiled)
     try:
-        g = (pkg.babybear.System if BABYBEAR else pkg.System)(ctx, blob, len(compiled))
+        g = (pkg.babybear.System if babybear else pkg.System)(ctx, blob, len(compiled))
     except pkg.MstarkError as e:
         o_failed = False
         try:
@@ -142,6 +152,8 @@ def one_case(pkg, fe, oracle, ctx, rng, case):
             o_failed = True
         assert o_failed, "library rejected a system the oracle accepts: %s" % e
         return "rejected-by-both"
+    if on_system is not None:
+        on_system(g)
     o = oracle.System(g.blob)
     try:
         want = o.prove(traces, packed)
@@ -156,7 +168,7 @@ def one_case(pkg, fe, oracle, ctx, rng, case):
     assert got == want, "case %d: proof bytes differ (len %d vs %d)" % (case, len(got), len(want))
     if os.environ.get("FUZZ_LEVEL2"):
         sys.path.insert(0, os.path.join(ROOT, "tests")) if os.path.join(ROOT, "tests") not in sys.path else None
-        if BABYBEAR:
+        if babybear:
             import test_gpu_bb_level2 as l2
 
             g.n_circuits = len(compiled)
@@ -196,11 +208,9 @@ def main():
     fe = pkg.frontend
     global KPERM
     if BABYBEAR:
-        import contextlib
         import oracle_bb as oracle
         KPERM = fe.poseidon2_constants()
     else:
-        import contextlib
         import oracle
 
     ctx = pkg.Context(0)
