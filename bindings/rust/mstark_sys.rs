@@ -109,6 +109,8 @@ extern "C" {
     pub fn ms_prove(sys: *mut ms_system, w: *mut ms_witness, proof_out: *mut u8, cap: usize, proof_len: *mut usize, stage_ms: *mut f64) -> i32;
     pub fn ms_verify(sys: *mut ms_system, n_claims: usize, claim_offsets: *const u64, claim_data: *const u64, proof: *const u8,
                      proof_len: usize, verdict: *mut i32) -> i32;
+    pub fn ms_verify_batch(sys: *mut ms_system, n_proofs: usize, n_claims: *const u64, claim_offsets: *const *const u64,
+                           claim_data: *const *const u64, proofs: *const *const u8, proof_lens: *const u64, verdicts: *mut i32) -> i32;
     pub fn ms_prove_sharded(sys: *mut ms_system, w: *mut ms_witness, comm: *const ms_comm, owners: *const i32, proof_out: *mut u8,
                             cap: usize, proof_len: *mut usize, stage_ms: *mut f64) -> i32;
     pub fn ms_ctx_comm_progress(ctx: *mut ms_ctx, out: *mut c_char, cap: usize, seq: *mut u64, in_flight: *mut i32) -> i32;
@@ -130,6 +132,8 @@ extern "C" {
     pub fn ms_mmcs_commit(ctx: *mut ms_ctx, n: usize, mats: *const *const u64, heights: *const u64, widths: *const u64, cap_height: u32,
                           cap_out: *mut u8, out: *mut *mut ms_mmcs) -> i32;
     pub fn ms_mmcs_open(m: *mut ms_mmcs, index: usize, vals_out: *mut u64, proof_out: *mut u8, n_siblings: *mut usize) -> i32;
+    pub fn ms_mmcs_verify_batch(ctx: *mut ms_ctx, n_mats: usize, heights: *const u64, widths: *const u64, cap: *const u8, cap_height: u32,
+                                n_openings: usize, indices: *const u64, vals: *const u64, siblings: *const u8, ok_out: *mut u8) -> i32;
     pub fn ms_mmcs_destroy(m: *mut ms_mmcs);
     pub fn ms_blake3(ctx: *mut ms_ctx, bytes: *const u8, len: usize, out32: *mut u8) -> i32;
     pub fn ms_challenger_create(params7: *const u64, out: *mut *mut ms_challenger) -> i32;

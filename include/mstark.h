@@ -169,6 +169,17 @@ int32_t ms_prove(ms_system* sys, ms_witness* w, uint8_t* proof_out, size_t cap, 
 #define MS_VERDICT_UNBALANCED 6
 int32_t ms_verify(ms_system* sys, size_t n_claims, const uint64_t* claim_offsets, const uint64_t* claim_data,
                   const uint8_t* proof, size_t proof_len, int32_t* verdict);
+/* N proofs of ONE ms_system. verdicts[i] is what ms_verify writes for proof i (MS_VERDICT_*), for every input.
+ * Claims are given per proof as in ms_verify (claim_offsets[i] / claim_data[i] may be NULL where n_claims[i] = 0).
+ * n_proofs = 0 is MS_OK. A null proof pointer or null verdicts is MS_ERR. Nothing in a proof's bytes can make the call fail
+ * or fault: a malformed proof is a verdict. Per proof the host parses, checks the shape, replays the transcript, checks both
+ * proofs of work, the arity schedule and the constraints at zeta; the per-query arithmetic (reduced openings, FRI fold
+ * chain, final polynomial) and every Merkle path of the batch run on the device in two launches, with one host wait per
+ * call (per 256 MB of openings) when the claims stay below 8192 transcript words. MS_ERR for a system whose traces of one
+ * kind are together wider than 8192 columns (one leaf is hashed inside a thread). */
+int32_t ms_verify_batch(ms_system* sys, size_t n_proofs, const uint64_t* n_claims, const uint64_t* const* claim_offsets,
+                        const uint64_t* const* claim_data, const uint8_t* const* proofs, const uint64_t* proof_lens,
+                        int32_t* verdicts);
 
 /* ---- One proof over several GPUs (one process per GPU; SURVEY §8e, BASELINE config 3). The reference has no such
  * mode: this is System::prove_multiple_claims (src/prover.rs:290-603) with the Pcs::commit / Pcs::open calls
@@ -312,6 +323,14 @@ int32_t ms_mmcs_commit(ms_ctx* ctx, size_t n, const uint64_t* const* mats, const
 /* open_batch(index): opened rows concatenated in matrix order; siblings bottom-up; *n_siblings written */
 int32_t ms_mmcs_open(ms_mmcs* m, size_t index, uint64_t* vals_out, uint8_t* proof_out, size_t* n_siblings);
 void ms_mmcs_destroy(ms_mmcs* m);
+/* MerkleTreeMmcs::verify_batch for many openings of one commitment at once, one device thread per opening. The commitment
+ * is described by its cap (32 << cap_height bytes, cap_height <= log2 of the tallest height) and the matrices' heights and
+ * widths. Opening k is indices[k], the opened rows concatenated in matrix order (sum of widths words each) and its siblings
+ * bottom-up ((log2 max height - cap_height) * 32 bytes each): the layout ms_mmcs_open writes. ok_out[k] = 1 / 0; an index
+ * beyond the tallest height or a non-canonical value is refused (0). n_openings = 0 is MS_OK. */
+int32_t ms_mmcs_verify_batch(ms_ctx* ctx, size_t n_mats, const uint64_t* heights, const uint64_t* widths, const uint8_t* cap,
+                             uint32_t cap_height, size_t n_openings, const uint64_t* indices, const uint64_t* vals,
+                             const uint8_t* siblings, uint8_t* ok_out);
 int32_t ms_blake3(ms_ctx* ctx, const uint8_t* bytes, size_t len, uint8_t out32[32]);
 
 /* ---- Pcs::commit / Pcs::open / Pcs::verify on their own (examples/pcs_example.rs:64-121; the calls of src/prover.rs:350,419,580

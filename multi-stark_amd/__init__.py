@@ -46,8 +46,8 @@ def exported_symbols():
             "ms_system_destroy", "ms_system_preprocessed_commit", "ms_system_circuit_info", "ms_system_circuit_kernels", "ms_witness_create", "ms_witness_create_host", "ms_claims_slice_range", "ms_witness_create_host_sliced", "ms_witness_prefetch",
             "ms_witness_u32_add_bench", "ms_witness_destroy", "ms_prove", "ms_prove_sharded", "ms_ctx_comm_progress", "ms_comm_rccl_unique_id", "ms_comm_rccl_create",
             "ms_comm_rccl_table", "ms_comm_rccl_bytes_moved", "ms_comm_rccl_destroy", "ms_comm_local_group_create", "ms_comm_local_group_abort",
-            "ms_comm_local_group_destroy", "ms_comm_local_create", "ms_comm_local_table", "ms_comm_local_bytes_moved", "ms_comm_local_destroy", "ms_verify", "ms_dft_batch", "ms_coset_lde_batch", "ms_quotient_lde", "ms_mmcs_commit",
-            "ms_mmcs_open", "ms_mmcs_destroy", "ms_blake3", "ms_pcs_commit", "ms_pcs_open", "ms_pcs_verify", "ms_challenger_create",
+            "ms_comm_local_group_destroy", "ms_comm_local_create", "ms_comm_local_table", "ms_comm_local_bytes_moved", "ms_comm_local_destroy", "ms_verify", "ms_verify_batch", "ms_dft_batch", "ms_coset_lde_batch", "ms_quotient_lde", "ms_mmcs_commit",
+            "ms_mmcs_open", "ms_mmcs_destroy", "ms_mmcs_verify_batch", "ms_blake3", "ms_pcs_commit", "ms_pcs_open", "ms_pcs_verify", "ms_challenger_create",
             "ms_challenger_destroy", "ms_challenger_observe", "ms_challenger_observe_digests", "ms_challenger_sample_ext",
             "ms_challenger_sample_bits", "ms_stage2_trace", "ms_claims_accumulator",
             "ms_quotient_values", "ms_field_op", "ms_trace_destroy", "ms_trace_info", "ms_system_preprocessed_mmcs",
@@ -230,10 +230,41 @@ class Mmcs:
         _check(lib().ms_mmcs_open(self.h, C.c_size_t(index), _p(vals), _b(proof), C.byref(ns)))
         return vals, proof[: 32 * ns.value].tobytes()
 
+    def verify_batch(self, indices, vals, siblings):
+        """MerkleTreeMmcs::verify_batch of many openings of this commitment on the device (ms_mmcs_verify_batch): per
+        opening its index, the values and the sibling bytes `open` returns. -> np.ndarray of 0 / 1"""
+        hs = [m.shape[0] for m in self.mats]
+        return mmcs_verify_batch(self.ctx, self.cap, len(self.cap) // 32, hs, self.widths, indices, vals, siblings)
+
     def __del__(self):
         if getattr(self, "h", None):
             lib().ms_mmcs_destroy(self.h)
             self.h = None
+
+
+def mmcs_verify_batch(ctx, cap, cap_size, heights, widths, indices, vals, siblings):
+    """ms_mmcs_verify_batch without an Mmcs: the commitment is its cap (`cap_size` digests), heights and widths.
+    indices: n integers; vals: per opening the rows concatenated in matrix order; siblings: per opening its path bytes."""
+    hs, ws = _u64(heights), _u64(widths)
+    idx = _u64(indices)
+    n = idx.size
+    rw = int(ws.sum())
+    cap_height = int(cap_size).bit_length() - 1
+    if cap_size != 1 << cap_height or len(cap) != 32 * cap_size:
+        raise MstarkError("a cap holds a power-of-two number of 32-byte digests")
+    path = max(int(hs.max()).bit_length() - 1 - cap_height, 0) if hs.size else 0
+    v = np.zeros(max(n * rw, 1), dtype=np.uint64)
+    if n * rw:
+        v[: n * rw] = np.concatenate([_u64(x).ravel() for x in vals]) if not isinstance(vals, np.ndarray) else _u64(vals).ravel()
+    sib_bytes = b"".join(bytes(s) for s in siblings) if not isinstance(siblings, (bytes, bytearray, np.ndarray)) else bytes(siblings)
+    if len(sib_bytes) != n * path * 32:
+        raise MstarkError("expected %d sibling bytes per opening" % (path * 32))
+    sib = np.frombuffer(sib_bytes + b"\0", dtype=np.uint8)
+    capb = np.frombuffer(bytes(cap), dtype=np.uint8)
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    _check(lib().ms_mmcs_verify_batch(ctx.h, C.c_size_t(hs.size), _p(hs), _p(ws), _b(capb), C.c_uint32(cap_height), C.c_size_t(n),
+                                      _p(idx if n else np.zeros(1, dtype=np.uint64)), _p(v), _b(sib), _b(ok)))
+    return ok[:n].copy()
 
 
 class DeviceCommitment(Mmcs):
@@ -608,6 +639,29 @@ class System:
         return int(verdict.value)
 
     verify = verify_multiple_claims
+
+    def verify_batch(self, items):
+        """ms_verify_batch: `items` is a list of (claims_packed, proof), proofs as in verify_multiple_claims. -> the list of
+        verdicts verify_multiple_claims gives one by one; the per-query arithmetic and the Merkle paths of the whole batch run
+        on the device."""
+        n = len(items)
+        if n == 0:
+            _check(lib().ms_verify_batch(self.h, C.c_size_t(0), None, None, None, None, None, None))
+            return []
+        keep, lens, ncl = [], np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        offp, datp, prp = (u64p * n)(), (u64p * n)(), (u8p * n)()
+        for i, (claims_packed, proof) in enumerate(items):
+            data = proof.to_bytes() if isinstance(proof, Proof) else bytes(proof)
+            buf = np.frombuffer(data + b"\0", dtype=np.uint8)  # (a zero-length proof still needs an address)
+            offs, cd = claims_packed
+            offs = _u64(offs)
+            cd = _u64(cd) if len(cd) else np.zeros(1, dtype=np.uint64)
+            keep.append((buf, offs, cd))
+            lens[i], ncl[i] = len(data), len(offs) - 1
+            offp[i], datp[i], prp[i] = _p(offs), _p(cd), _b(buf)
+        verdicts = np.full(n, -1, dtype=np.int32)
+        _check(lib().ms_verify_batch(self.h, C.c_size_t(n), _p(ncl), offp, datp, prp, _p(lens), verdicts.ctypes.data_as(C.POINTER(C.c_int32))))
+        return [int(v) for v in verdicts]
 
     def prove_sharded(self, witness, comm, owners, want_times=False):
         """The same Proof computed by `comm.world` ranks (ms_prove_sharded; see multi-stark_amd/sharded.py for `comm`).

@@ -383,6 +383,33 @@ int32_t ms_verify(ms_system* sys, size_t n_claims, const uint64_t* claim_offsets
   MS_CATCH
 }
 
+int32_t ms_verify_batch(ms_system* sys, size_t n_proofs, const uint64_t* n_claims, const uint64_t* const* claim_offsets,
+                        const uint64_t* const* claim_data, const uint8_t* const* proofs, const uint64_t* proof_lens, int32_t* verdicts) {
+  MS_TRY if (n_proofs == 0) return MS_OK;
+  if (!sys || !verdicts || !proofs || !proof_lens || !n_claims) throw std::runtime_error("ms_verify_batch: null argument");
+  for (size_t i = 0; i < n_proofs; i++) {
+    if (!proofs[i]) throw std::runtime_error("ms_verify_batch: null proof");
+    if (n_claims[i]) {
+      if (!claim_offsets || !claim_offsets[i] || !claim_data) throw std::runtime_error("ms_verify_batch: null claims");
+      if (claim_offsets[i][0] != 0) throw std::runtime_error("claim offsets must start at 0");
+      if (claim_offsets[i][n_claims[i]] && !claim_data[i]) throw std::runtime_error("ms_verify_batch: null claims");
+    }
+  }
+  verify_batch(*sys->sys, n_proofs, n_claims, claim_offsets, claim_data, proofs, proof_lens, verdicts);
+  return MS_OK;
+  MS_CATCH
+}
+
+int32_t ms_mmcs_verify_batch(ms_ctx* c, size_t n_mats, const uint64_t* heights, const uint64_t* widths, const uint8_t* cap, uint32_t cap_height,
+                             size_t n_openings, const uint64_t* indices, const uint64_t* vals, const uint8_t* siblings, uint8_t* ok_out) {
+  MS_TRY if (n_openings == 0) return MS_OK;
+  if (!c || !heights || !widths || !cap || !indices || !vals || !siblings || !ok_out) throw std::runtime_error("ms_mmcs_verify_batch: null argument");
+  std::vector<size_t> hs(heights, heights + n_mats), ws(widths, widths + n_mats);
+  mmcs_verify_batch_device(c->ctx, hs, ws, cap, cap_height, n_openings, indices, vals, siblings, ok_out);
+  return MS_OK;
+  MS_CATCH
+}
+
 int32_t ms_dft_batch(ms_ctx* c, const uint64_t* in, size_t h, size_t w, int32_t inverse, uint64_t* out) {
   MS_TRY Ctx& ctx = c->ctx;
   HIP_CHECK(hipSetDevice(ctx.device));

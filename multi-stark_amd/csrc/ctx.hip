@@ -324,6 +324,7 @@ Ctx::~Ctx() {
   for (auto& kv : lde_scales) (void)hipFree(kv.second);
   if (pinned) (void)hipHostFree(pinned);
   if (bounce) (void)hipHostFree(bounce);
+  if (verify_stage) (void)hipHostFree(verify_stage);
   if (tw0) (void)hipFree(tw0);
   if (twc) (void)hipFree(twc);
   if (twf) (void)hipFree(twf);

@@ -173,6 +173,15 @@ std::vector<uint8_t> prove_sharded(HSystem& sys, HWitness& w, const ms_comm_t* c
 // System::verify_multiple_claims (verifier.hip): 0 = accepted, otherwise the VerificationError code of include/mstark.h
 int verify(HSystem& sys, size_t n_claims, const u64* claim_offsets, const u64* claim_data, const uint8_t* proof, size_t proof_len);
 
+// the same for n_proofs proofs of one system with the per-query arithmetic and every Merkle path on the device (verifier.hip,
+// verify_dev.hip): verdicts[i] is what verify() returns for proof i
+void verify_batch(HSystem& sys, size_t n_proofs, const u64* n_claims, const u64* const* claim_offsets, const u64* const* claim_data,
+                  const uint8_t* const* proofs, const u64* proof_lens, int32_t* verdicts);
+// MerkleTreeMmcs::verify_batch for many openings of one commitment, one device thread per opening
+void mmcs_verify_batch_device(Ctx& ctx, const std::vector<size_t>& heights, const std::vector<size_t>& widths, const uint8_t* cap,
+                              unsigned cap_height, size_t n_openings, const u64* indices, const u64* vals, const uint8_t* siblings,
+                              uint8_t* ok_out);
+
 // Pcs::open / Pcs::verify on their own (prover.hip, verifier.hip)
 void pcs_open_standalone(Ctx& ctx, const Params& prm, const std::vector<PcsData*>& data, const std::vector<std::vector<std::vector<E2>>>& points,
                          Challenger& ch, std::vector<E2>& opened_flat, std::vector<uint8_t>& fri_bytes);

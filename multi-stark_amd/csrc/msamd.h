@@ -114,6 +114,10 @@ struct Ctx {
   // address in round 4's fuzzing)
   uint8_t* bounce = nullptr;
   static constexpr size_t BOUNCE_BYTES = size_t(4) << 20;
+  // page-locked staging of batched verification (verifier.hip): a whole batch's arrays go up in ONE asynchronous copy, so
+  // the number of host waits of ms_verify_batch does not grow with the batch. Grows on demand, reused by later calls.
+  uint8_t* verify_stage = nullptr;
+  size_t verify_stage_cap = 0;
   void bounce_h2d(void* dst, const void* src, size_t n, hipStream_t on = nullptr);  // on: another stream than `stream`
   void bounce_d2h(void* dst, const void* src, size_t n);
   struct PendingD2H {
