@@ -188,6 +188,8 @@ extern "C" {
                       stage_ms: *mut f64) -> i32;
     pub fn msbb_verify(sys: *mut msbb_system, n_claims: usize, claim_offsets: *const u64, claim_data: *const u32, proof: *const u8,
                        proof_len: usize, verdict: *mut i32) -> i32;
+    pub fn msbb_verify_batch(sys: *mut msbb_system, n_proofs: usize, n_claims: *const u64, claim_offsets: *const *const u64,
+                             claim_data: *const *const u32, proofs: *const *const u8, proof_lens: *const u64, verdicts: *mut i32) -> i32;
     pub fn msbb_set_poseidon2(ctx: *mut ms_ctx, constants141: *const u32) -> i32;
     pub fn msbb_poseidon2_permute(ctx: *mut ms_ctx, states: *mut u32, n: usize) -> i32;
     pub fn msbb_dft_batch(ctx: *mut ms_ctx, input: *const u32, h: usize, w: usize, inverse: i32, out: *mut u32) -> i32;
@@ -195,6 +197,8 @@ extern "C" {
     pub fn msbb_mmcs_commit(ctx: *mut ms_ctx, n: usize, mats: *const *const u32, heights: *const u64, widths: *const u64,
                             cap_height: u32, cap_out: *mut u32, out: *mut *mut msbb_mmcs) -> i32;
     pub fn msbb_mmcs_open(m: *mut msbb_mmcs, index: usize, vals_out: *mut u32, proof_out: *mut u32, n_siblings: *mut usize) -> i32;
+    pub fn msbb_mmcs_verify_batch(ctx: *mut ms_ctx, n_mats: usize, heights: *const u64, widths: *const u64, cap: *const u32, cap_height: u32,
+                                  n_openings: usize, indices: *const u64, vals: *const u32, siblings: *const u32, ok_out: *mut u8) -> i32;
     pub fn msbb_mmcs_destroy(m: *mut msbb_mmcs);
     pub fn msbb_field_op(ctx: *mut ms_ctx, op: i32, a: *const u32, b: *const u32, n: usize, out: *mut u32) -> i32;
     // Level 2 of the BabyBear configuration (include/mstark_bb.h)

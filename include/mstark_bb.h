@@ -18,6 +18,7 @@
  *   msbb_mmcs_*      MerkleTreeMmcs<.., PaddingFreeSponge<Perm,16,8,8>, TruncatedPermutation<Perm,2,8,16>, 2, 8>   baby_bear_config.rs:30-33
  *   msbb_poseidon2_permute   Poseidon2BabyBear<16>::permute           baby_bear_config.rs:29
  *   msbb_verify      System::<SC>::verify_multiple_claims             src/verifier.rs:208-532
+ *   msbb_verify_batch        the same for N proofs, queries and Merkle paths on the device
  */
 #ifndef MSTARK_BB_H
 #define MSTARK_BB_H
@@ -65,6 +66,17 @@ int32_t msbb_prove(msbb_system* sys, msbb_witness* w, uint8_t* proof_out, size_t
 int32_t msbb_verify(msbb_system* sys, size_t n_claims, const uint64_t* claim_offsets, const uint32_t* claim_data,
                     const uint8_t* proof, size_t proof_len, int32_t* verdict);
 
+/* msbb_verify for N proofs of ONE system: verdicts[i] is what msbb_verify writes for (claims i, proof i), for every input.
+ * Claims: per proof its count, its offset table (n_claims[i] + 1 entries) and its data; claim_offsets[i] / claim_data[i] may
+ * be null where n_claims[i] = 0. n_proofs = 0 is MS_OK. A null proof pointer or null verdicts is MS_ERR. Nothing in a proof's
+ * bytes can make the call fail or fault: a malformed proof is a verdict. Per proof the host parses, checks the shape, replays
+ * the duplex transcript, checks both proofs of work, the arity schedule and the constraints at zeta; the per-query
+ * arithmetic (reduced openings, FRI fold chain, final polynomial) and every Merkle path of the batch run on the device in
+ * two launches, with one host wait per call (per 256 MB of openings). */
+int32_t msbb_verify_batch(msbb_system* sys, size_t n_proofs, const uint64_t* n_claims, const uint64_t* const* claim_offsets,
+                          const uint32_t* const* claim_data, const uint8_t* const* proofs, const uint64_t* proof_lens,
+                          int32_t* verdicts);
+
 /* ---- PCS-level entry points (host buffers in and out, canonical u32) */
 /* the permutation used by msbb_poseidon2_permute / msbb_mmcs_commit: 141 canonical round constants */
 int32_t msbb_set_poseidon2(ms_ctx* ctx, const uint32_t* constants141);
@@ -79,6 +91,15 @@ int32_t msbb_mmcs_commit(ms_ctx* ctx, size_t n, const uint32_t* const* mats, con
 /* opened rows concatenated in matrix order; siblings bottom-up, 8 words each */
 int32_t msbb_mmcs_open(msbb_mmcs* m, size_t index, uint32_t* vals_out, uint32_t* proof_out, size_t* n_siblings);
 void msbb_mmcs_destroy(msbb_mmcs* m);
+/* MerkleTreeMmcs::verify_batch for many openings of one commitment at once, one device thread per opening, with the
+ * permutation of msbb_set_poseidon2. The commitment is described by its cap (8 << cap_height words, cap_height <= log2 of
+ * the tallest height) and the matrices' heights and widths. Opening k is indices[k], the opened rows concatenated in matrix
+ * order (sum of widths words each) and its siblings bottom-up ((log2 max height - cap_height) * 8 words each): the layout
+ * msbb_mmcs_open writes. ok_out[k] = 1 / 0; an index beyond the tallest height, or a value or digest word >= p, is refused
+ * (0). n_openings = 0 is MS_OK. */
+int32_t msbb_mmcs_verify_batch(ms_ctx* ctx, size_t n_mats, const uint64_t* heights, const uint64_t* widths, const uint32_t* cap,
+                               uint32_t cap_height, size_t n_openings, const uint64_t* indices, const uint32_t* vals,
+                               const uint32_t* siblings, uint8_t* ok_out);
 /* op 0 add, 1 sub, 2 mul, 3 inverse(a), 4 ext4 mul (quads), 5 ext4 inverse (quads) */
 int32_t msbb_field_op(ms_ctx* ctx, int32_t op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
 

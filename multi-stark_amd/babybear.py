@@ -18,8 +18,8 @@ P = frontend.BABYBEAR["P"]
 def exported_symbols():
     """Every entry point include/mstark_bb.h declares (used by the CPU-side ABI test)."""
     return ["msbb_system_create", "msbb_system_destroy", "msbb_system_preprocessed_commit", "msbb_system_circuit_info", "msbb_system_circuit_kernels",
-            "msbb_witness_create", "msbb_witness_create_host", "msbb_witness_destroy", "msbb_prove", "msbb_verify", "msbb_set_poseidon2", "msbb_poseidon2_permute",
-            "msbb_dft_batch", "msbb_coset_lde_batch", "msbb_mmcs_commit", "msbb_mmcs_open", "msbb_mmcs_destroy", "msbb_field_op",
+            "msbb_witness_create", "msbb_witness_create_host", "msbb_witness_destroy", "msbb_prove", "msbb_verify", "msbb_verify_batch", "msbb_set_poseidon2", "msbb_poseidon2_permute",
+            "msbb_dft_batch", "msbb_coset_lde_batch", "msbb_mmcs_commit", "msbb_mmcs_open", "msbb_mmcs_verify_batch", "msbb_mmcs_destroy", "msbb_field_op",
             "msbb_challenger_create", "msbb_challenger_destroy", "msbb_challenger_observe", "msbb_challenger_observe_digests",
             "msbb_challenger_sample_ext", "msbb_challenger_sample_bits", "msbb_challenger_observe_claims", "msbb_trace_destroy", "msbb_trace_info",
             "msbb_system_preprocessed_mmcs", "msbb_witness_commit_stage1", "msbb_witness_claims_accumulator", "msbb_stage2_build",
@@ -150,6 +150,30 @@ class System:
         return verdict.value
 
     verify = verify_multiple_claims
+
+    def verify_batch(self, items):
+        """msbb_verify_batch: `items` is a list of (claims_packed, proof), proofs as in verify_multiple_claims. -> the list of
+        verdicts verify_multiple_claims gives one by one; the per-query arithmetic and the Merkle paths of the whole batch run
+        on the device."""
+        n = len(items)
+        if n == 0:
+            _check(_lib().msbb_verify_batch(self.h, C.c_size_t(0), None, None, None, None, None, None))
+            return []
+        keep, lens, ncl = [], np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        offp, datp, prp = (u64p * n)(), (u32p * n)(), (u8p * n)()
+        for i, (claims_packed, proof) in enumerate(items):
+            data = proof.to_bytes() if isinstance(proof, Proof) else bytes(proof)
+            buf = np.frombuffer(data + b"\0", dtype=np.uint8)  # (a zero-length proof still needs an address)
+            offs, cd = claims_packed
+            offs = np.ascontiguousarray(offs, dtype=np.uint64)
+            cd = np.ascontiguousarray(cd, dtype=np.uint32) if len(cd) else np.zeros(1, dtype=np.uint32)
+            keep.append((buf, offs, cd))
+            lens[i], ncl[i] = len(data), len(offs) - 1
+            offp[i], datp[i], prp[i] = offs.ctypes.data_as(u64p), _p32(cd), buf.ctypes.data_as(u8p)
+        verdicts = np.full(n, -1, dtype=np.int32)
+        _check(_lib().msbb_verify_batch(self.h, C.c_size_t(n), ncl.ctypes.data_as(u64p), offp, datp, prp, lens.ctypes.data_as(u64p),
+                                        verdicts.ctypes.data_as(C.POINTER(C.c_int32))))
+        return [int(v) for v in verdicts]
 
     def prove_multiple_claims(self, witness, want_times=False):
         times = np.zeros(6, dtype=np.float64)
@@ -380,10 +404,50 @@ class Mmcs:
         _check(_lib().msbb_mmcs_open(self.h, C.c_size_t(index), _p32(vals), _p32(proof), C.byref(k)))
         return vals, proof[: 8 * k.value].copy()
 
+    def verify_batch(self, indices, vals, siblings):
+        """MerkleTreeMmcs::verify_batch of many openings of this commitment on the device (msbb_mmcs_verify_batch): per
+        opening its index, the values and the sibling words `open` returns. -> np.ndarray of 0 / 1"""
+        hs = [m.shape[0] for m in self.mats]
+        return mmcs_verify_batch(self.ctx, self.cap, self.cap.size // 8, hs, self.widths, indices, vals, siblings)
+
     def __del__(self):
         if getattr(self, "h", None):
             _lib().msbb_mmcs_destroy(self.h)
             self.h = None
+
+
+def _raw32(a):
+    """u32 words as they are: a word >= p is the entry point's to refuse, not an error of the call"""
+    return np.ascontiguousarray(np.asarray(a).ravel(), dtype=np.uint32)
+
+
+def mmcs_verify_batch(ctx, cap, cap_size, heights, widths, indices, vals, siblings):
+    """msbb_mmcs_verify_batch without an Mmcs: the commitment is its cap (`cap_size` digests of 8 words), heights and widths.
+    indices: n integers; vals: per opening the rows concatenated in matrix order; siblings: per opening its path words."""
+    hs = np.ascontiguousarray(heights, dtype=np.uint64)
+    ws = np.ascontiguousarray(widths, dtype=np.uint64)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64)
+    n = idx.size
+    rw = int(ws.sum())
+    cap = _raw32(cap)
+    cap_height = int(cap_size).bit_length() - 1
+    if cap_size != 1 << cap_height or cap.size != 8 * cap_size:
+        raise _pkg().MstarkError("a cap holds a power-of-two number of 8-word digests")
+    path = max(int(hs.max()).bit_length() - 1 - cap_height, 0) if hs.size else 0
+    v = np.zeros(max(n * rw, 1), dtype=np.uint32)
+    if n * rw:
+        v[: n * rw] = np.concatenate([_raw32(x) for x in vals]) if not isinstance(vals, np.ndarray) else _raw32(vals)
+    sib = np.zeros(max(n * path * 8, 1), dtype=np.uint32)
+    flat = (np.concatenate([_raw32(s) for s in siblings]) if not isinstance(siblings, np.ndarray) else _raw32(siblings)) if n else np.zeros(0, dtype=np.uint32)
+    if flat.size != n * path * 8:
+        raise _pkg().MstarkError("expected %d sibling words per opening" % (path * 8))
+    sib[: flat.size] = flat
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    _check(_lib().msbb_mmcs_verify_batch(ctx.h, C.c_size_t(hs.size), hs.ctypes.data_as(u64p), ws.ctypes.data_as(u64p), _p32(cap),
+                                         C.c_uint32(cap_height), C.c_size_t(n),
+                                         (idx if n else np.zeros(1, dtype=np.uint64)).ctypes.data_as(u64p), _p32(v), _p32(sib),
+                                         ok.ctypes.data_as(u8p)))
+    return ok[:n].copy()
 
 
 def field_op(ctx, op, a, b=None):

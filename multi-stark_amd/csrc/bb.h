@@ -128,5 +128,8 @@ struct GatherSeg {
 };
 void bb_gather(Ctx& ctx, const std::vector<GatherSeg>& segs, std::vector<u32>& out);
 void bb_field_op(Ctx& ctx, int op, const u32* a, const u32* b, size_t n, u32* out);
+// ---- batched verification (bb_verify_dev.h): the arithmetic launch over n_queries threads, then the path launch over n_items threads
+struct BVDev;
+void bbv_launch(Ctx& ctx, const BVDev& d, size_t n_queries, size_t n_items, double path_bytes);
 
 }  // namespace msbb

@@ -10,6 +10,7 @@
 
 #include "../../include/mstark_bb.h"
 #include "bb.h"
+#include "bb_verify_dev.h"
 
 namespace msbb {
 
@@ -1459,13 +1460,25 @@ void coord_mul_e(const E4* a, const E4* b, E4* out) {
   const u32 w = bb_to_monty(BB_EXT_W);
   for (int k = 0; k < 4; k++) out[k] = e4_add(lo[k], e4_mul_base(hi[k], w));
 }
-}  // namespace
 
-int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* claim_data, const uint8_t* proof_bytes, size_t proof_len) {
+// What verify() knows of one proof once the transcript has been replayed up to zeta: the parsed proof, the challenges, the
+// PCS rounds to check (they point into `proof`) and the challenger in the state Pcs::verify starts from.
+struct Prepared {
+  VProof proof;
+  std::vector<size_t> aidx, qdeg;
+  E4 beta, gamma, acc, alpha, zeta;
+  std::vector<RoundClaim> rounds;
+  Challenger ch;
+  explicit Prepared(const Poseidon2* perm) : ch(perm) {}
+};
+
+// parse, verify_shape and the transcript replay: V_OK, or the verdict that ends the verification here
+int verify_prepare(const BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* claim_data, const uint8_t* proof_bytes,
+                   size_t proof_len, Prepared& P) {
   const Params& prm = sys.params;
   const size_t C = sys.circuits.size();
   if (C == 0) return V_INVALID_SYSTEM;
-  VProof proof;
+  VProof& proof = P.proof;
   try {
     proof = parse_proof(proof_bytes, proof_len);
   } catch (const Malformed&) {
@@ -1473,7 +1486,7 @@ int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* c
   }
   // ---- verify_shape (src/verifier.rs:536-695)
   if (proof.active.size() != C) return V_INVALID_SHAPE;
-  std::vector<size_t> aidx;
+  std::vector<size_t>& aidx = P.aidx;
   std::vector<int> apos(C, -1);
   for (size_t i = 0; i < C; i++)
     if (proof.active[i]) {
@@ -1489,7 +1502,7 @@ int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* c
   for (size_t ci = 0; ci < C; ci++)
     if (sys.pre_indices[ci] >= 0 && !proof.active[ci] && proof.pre_opened[sys.pre_indices[ci]].size() != 0) return V_INVALID_SHAPE;
   if (proof.s1_opened.size() != na || proof.s2_opened.size() != na || proof.q_opened.size() != na) return V_INVALID_SHAPE;
-  std::vector<size_t> qdeg;
+  std::vector<size_t>& qdeg = P.qdeg;
   for (size_t pos = 0; pos < na; pos++) {
     const size_t ci = aidx[pos];
     const BCircuit& c = sys.circuits[ci];
@@ -1516,7 +1529,7 @@ int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* c
   const size_t claim_elems = n_claims ? (size_t)claim_offsets[n_claims] : 0;
   for (size_t i = 0; i < claim_elems; i++)
     if (claim_data[i] >= BB_P) return V_INVALID_SHAPE;
-  Challenger ch(&sys.perm);
+  Challenger& ch = P.ch;
   for (u32 v : sys.seed) ch.observe(v);
   ch.observe_usize(C);
   for (auto& c : sys.circuits) {
@@ -1532,13 +1545,14 @@ int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* c
     ch.observe_usize(claim_offsets[i + 1] - claim_offsets[i]);
     for (u64 k = claim_offsets[i]; k < claim_offsets[i + 1]; k++) ch.observe(bb_to_monty(claim_data[k]));
   }
-  const E4 beta = ch.sample_e4();
+  const E4 beta = P.beta = ch.sample_e4();
   ch.observe_e4(beta);
-  const E4 gamma = ch.sample_e4();
+  const E4 gamma = P.gamma = ch.sample_e4();
   ch.observe_e4(gamma);
   ch.observe_cap(proof.s2);
   for (auto& a : proof.accs) ch.observe_e4(a);
-  E4 acc = e4_zero();
+  E4& acc = P.acc;
+  acc = e4_zero();
   for (size_t i = 0; i < n_claims; i++) {
     E4 f = e4_zero();
     for (u64 k = claim_offsets[i + 1]; k-- > claim_offsets[i];) {
@@ -1549,11 +1563,12 @@ int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* c
     if (e4_is_zero(m)) return V_INVALID_SHAPE;  // the reference would divide by zero here
     acc = e4_add(acc, e4_inv(m));
   }
-  const E4 alpha = ch.sample_e4();
+  P.alpha = ch.sample_e4();
   ch.observe_cap(proof.q);
-  const E4 zeta = ch.sample_e4();
+  const E4 zeta = P.zeta = ch.sample_e4();
 
-  std::vector<RoundClaim> rounds(3);
+  std::vector<RoundClaim>& rounds = P.rounds;
+  rounds.assign(3, RoundClaim());
   rounds[0].commit = proof.s1, rounds[1].commit = proof.s2, rounds[2].commit = proof.q;
   for (size_t pos = 0; pos < na; pos++) {
     const unsigned ld = proof.log_degrees[pos];
@@ -1583,9 +1598,16 @@ int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* c
     }
     rounds.push_back(std::move(r0));
   }
-  if (!pcs_verify(sys, rounds, proof, ch)) return V_INVALID_OPENING;
+  return V_OK;
+}
 
-  // ---- out-of-domain check per circuit (src/verifier.rs:419-530)
+// the out-of-domain check per circuit (src/verifier.rs:419-530), after Pcs::verify has accepted
+int verify_ood(const BSystem& sys, const Prepared& P) {
+  const VProof& proof = P.proof;
+  const std::vector<size_t>&aidx = P.aidx, &qdeg = P.qdeg;
+  const size_t na = aidx.size();
+  const E4 beta = P.beta, gamma = P.gamma, alpha = P.alpha, zeta = P.zeta;
+  E4 acc = P.acc;
   for (size_t pos = 0; pos < na; pos++) {
     const size_t ci = aidx[pos];
     const BCircuit& c = sys.circuits[ci];
@@ -1685,6 +1707,492 @@ int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* c
     acc = next_acc;
   }
   return V_OK;
+}
+
+}  // namespace
+
+int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* claim_data, const uint8_t* proof_bytes, size_t proof_len) {
+  Prepared P(&sys.perm);
+  const int v = verify_prepare(sys, n_claims, claim_offsets, claim_data, proof_bytes, proof_len, P);
+  if (v != V_OK) return v;
+  if (!pcs_verify(sys, P.rounds, P.proof, P.ch)) return V_INVALID_OPENING;
+  return verify_ood(sys, P);
+}
+
+// ---------------------------------------------------------------- batched verification (msbb_verify_batch, msbb_mmcs_verify_batch)
+// The host keeps what is serial or cheap - parsing, verify_shape, the transcript replay, both proof-of-work checks, the query
+// indices, the arity schedule and the out-of-domain check - and makes EVERY structural check of pcs_verify before a value is
+// read. What remains per query (reduced openings, fold chain, final polynomial) and per Merkle path goes to the device as flat
+// arrays whose offsets all come from the lengths validated here (bb_verify_dev.h); a proof refused on the host adds nothing to them.
+namespace {
+
+struct BVBatch {
+  std::vector<u32> words, u32s, qmap;
+  std::vector<E4> ext;
+  std::vector<Digest8> digs;
+  std::vector<BVPathItem> items;
+  std::vector<BVProofDesc> proofs;
+  std::vector<BVMatDesc> mats;
+  std::vector<BVHeightDesc> heights;
+  size_t n_flags = 0, fri_words = 0, ro_count = 0;
+  double path_bytes = 0;
+  size_t bytes() const {
+    return (words.size() + u32s.size() + qmap.size() + fri_words) * 4 + (ext.size() + ro_count) * sizeof(E4) + digs.size() * sizeof(Digest8) +
+           items.size() * sizeof(BVPathItem);
+  }
+};
+const size_t BV_FLUSH_BYTES = size_t(256) << 20;  // a batch larger than this goes to the device in several parts
+
+struct PathPlan {
+  std::vector<size_t> order;  // the matrices in walk order: stable by descending height
+  std::vector<u32> groups;    // per level 0 .. path_len: 1 + words of the matrices of height max >> level, 0 = none
+  unsigned log_max = 0;
+};
+// everything mmcs_verify_batch refuses without hashing, and the walk order of what it would hash: false = refused
+bool mmcs_plan(const std::vector<Dim>& dims, size_t capn, size_t path_len, PathPlan& pl) {
+  if (dims.empty()) return false;
+  pl.order.resize(dims.size());
+  for (size_t i = 0; i < dims.size(); i++) {
+    pl.order[i] = i;
+    if (dims[i].h == 0 || (dims[i].h & (dims[i].h - 1))) return false;
+  }
+  std::stable_sort(pl.order.begin(), pl.order.end(), [&](size_t a, size_t b) { return dims[a].h > dims[b].h; });
+  pl.log_max = log2_strict(dims[pl.order[0]].h);
+  if (capn == 0 || (capn & (capn - 1))) return false;
+  const unsigned ch = log2_strict(capn);
+  if (ch > pl.log_max || path_len != pl.log_max - ch) return false;
+  std::vector<u64> gw(path_len + 1, 0);
+  std::vector<uint8_t> present(path_len + 1, 0);
+  for (size_t i : pl.order) {
+    const size_t k = pl.log_max - log2_strict(dims[i].h);
+    if (k > path_len) return false;  // shorter than the cap layer: never injected (pos != order.size())
+    gw[k] += dims[i].w;
+    present[k] = 1;
+  }
+  pl.groups.assign(path_len + 1, 0);
+  for (size_t k = 0; k <= path_len; k++) {
+    if (gw[k] >= 0xffffffffu) return false;  // (no proof or caller can hold four billion words in one row)
+    if (present[k]) pl.groups[k] = 1 + (u32)gw[k];
+  }
+  return true;
+}
+
+// the FRI leaf rows live behind the uploaded words: settle the offsets that count from them
+void bvbatch_seal(BVBatch& B) {
+  for (auto& it : B.items)
+    if (it.fri_row) {
+      it.vals_off += B.words.size();
+      it.fri_row = 0;
+    }
+  for (auto& p : B.proofs) p.fri_off += B.words.size();
+}
+
+template <class T>
+size_t bv_place(size_t& off, size_t count) {
+  off = (off + 63) & ~size_t(63);
+  const size_t at = off;
+  off += count * sizeof(T);
+  return at;
+}
+
+// upload, two launches, one read-back: fail[flag] != 0 where a device check of that flag's owner failed
+void bvbatch_run(Ctx& ctx, const Poseidon2* d_perm, BVBatch& B, std::vector<u32>& fail) {
+  fail.assign(B.n_flags, 0);
+  if (B.items.empty() && B.qmap.empty()) return;
+  bvbatch_seal(B);
+  size_t off = 0;
+  const size_t at_items = bv_place<BVPathItem>(off, B.items.size()), at_proofs = bv_place<BVProofDesc>(off, B.proofs.size());
+  const size_t at_mats = bv_place<BVMatDesc>(off, B.mats.size()), at_heights = bv_place<BVHeightDesc>(off, B.heights.size());
+  const size_t at_u32s = bv_place<u32>(off, B.u32s.size()), at_qmap = bv_place<u32>(off, B.qmap.size());
+  const size_t at_ext = bv_place<E4>(off, B.ext.size()), at_digs = bv_place<Digest8>(off, B.digs.size());
+  const size_t at_fail = bv_place<u32>(off, B.n_flags), at_words = bv_place<u32>(off, B.words.size());
+  const size_t up = off;
+  off += B.fri_words * 4;
+  const size_t at_ro = bv_place<E4>(off, B.ro_count);
+  size_t total = 4096;
+  while (total < off) total <<= 1;  // few distinct sizes: the context's pool keeps blocks by exact size
+  if (ctx.verify_stage_cap < up) {
+    HIP_CHECK(hipStreamSynchronize(ctx.stream));
+    if (ctx.verify_stage) (void)hipHostFree(ctx.verify_stage);
+    ctx.verify_stage = nullptr;
+    ctx.verify_stage_cap = 0;
+    size_t cap = size_t(1) << 20;
+    while (cap < up) cap <<= 1;
+    HIP_CHECK(hipHostMalloc((void**)&ctx.verify_stage, cap, hipHostMallocDefault));
+    ctx.verify_stage_cap = cap;
+  }
+  uint8_t* st = ctx.verify_stage;
+  auto put = [&](size_t at, const void* src, size_t n) {
+    if (n) memcpy(st + at, src, n);
+  };
+  put(at_items, B.items.data(), B.items.size() * sizeof(BVPathItem));
+  put(at_proofs, B.proofs.data(), B.proofs.size() * sizeof(BVProofDesc));
+  put(at_mats, B.mats.data(), B.mats.size() * sizeof(BVMatDesc));
+  put(at_heights, B.heights.data(), B.heights.size() * sizeof(BVHeightDesc));
+  put(at_u32s, B.u32s.data(), B.u32s.size() * 4);
+  put(at_qmap, B.qmap.data(), B.qmap.size() * 4);
+  put(at_ext, B.ext.data(), B.ext.size() * sizeof(E4));
+  put(at_digs, B.digs.data(), B.digs.size() * sizeof(Digest8));
+  memset(st + at_fail, 0, B.n_flags * 4);
+  put(at_words, B.words.data(), B.words.size() * 4);
+  DBuf<uint8_t> dev(ctx, total);
+  HIP_CHECK(hipMemcpyAsync(dev.p, st, up, hipMemcpyHostToDevice, ctx.stream));
+  BVDev d;
+  d.items = (const BVPathItem*)(dev.p + at_items);
+  d.proofs = (const BVProofDesc*)(dev.p + at_proofs);
+  d.mats = (const BVMatDesc*)(dev.p + at_mats);
+  d.heights = (const BVHeightDesc*)(dev.p + at_heights);
+  d.u32s = (const u32*)(dev.p + at_u32s);
+  d.qmap = (const u32*)(dev.p + at_qmap);
+  d.ext = (const E4*)(dev.p + at_ext);
+  d.digs = (const Digest8*)(dev.p + at_digs);
+  d.fail = (u32*)(dev.p + at_fail);
+  d.words = (u32*)(dev.p + at_words);
+  d.ro = (E4*)(dev.p + at_ro);
+  d.perm = d_perm;
+  bbv_launch(ctx, d, B.qmap.size(), B.items.size(), B.path_bytes);
+  ctx.d2h(fail.data(), d.fail, B.n_flags * 4);  // the call's one host wait (the staging buffer is free again after it)
+}
+
+void bv_add_item(BVBatch& B, const PathPlan& pl, u64 vals_off, bool fri_row, u64 index, u32 sib_off, u32 cap_off, u32 grp_off, u32 flag) {
+  BVPathItem it;
+  it.vals_off = vals_off;
+  it.index = index;
+  it.sib_off = sib_off;
+  it.cap_off = cap_off;
+  it.grp_off = grp_off;
+  it.n_levels = (u32)(pl.groups.size() - 1);
+  it.flag = flag;
+  it.fri_row = fri_row ? 1 : 0;  // resolved by bvbatch_seal
+  B.items.push_back(it);
+  double w = 0;
+  for (u32 g : pl.groups) w += g ? g - 1 : 0;
+  B.path_bytes += 4 * w + 32.0 * (it.n_levels + 1);
+}
+
+// pcs_verify with the per-query arithmetic and the Merkle paths left to the device.
+//   COLLECT_REFUSED  pcs_verify returns false here, whatever the values are (nothing was added to B)
+//   COLLECT_QUEUED   the verdict is B's flag `flag` after bvbatch_run
+//   COLLECT_HOST     queries open a matrix that is opened at no point (the preprocessed trace of an inactive circuit) with
+//                    different widths. The padding-free sponge can hash such rows to one digest, so pcs_verify may accept
+//                    them; the flat layout has one width per matrix, and the caller runs pcs_verify itself on this proof
+//                    (nothing was added to B). No prover output has this form.
+enum { COLLECT_REFUSED = 0, COLLECT_QUEUED, COLLECT_HOST };
+int pcs_collect(const BSystem& sys, const std::vector<RoundClaim>& rounds, const VProof& proof, Challenger& ch, BVBatch& B, u32 flag) {
+  const Params& prm = sys.params;
+  const unsigned lb = (unsigned)prm.log_blowup;
+  for (auto& r : rounds)
+    for (auto& m : r.mats)
+      for (auto& pv : m)
+        for (auto& y : *pv.second) ch.observe_e4(y);
+  const E4 alpha = ch.sample_e4();
+  const size_t nrounds = proof.commits.size();
+  if (proof.pow.size() != nrounds) return COLLECT_REFUSED;
+  std::vector<unsigned> arities(nrounds, 1);
+  if (!proof.queries.empty()) {
+    if (proof.queries[0].steps.size() != nrounds) return COLLECT_REFUSED;
+    for (size_t i = 0; i < nrounds; i++) arities[i] = proof.queries[0].steps[i].log_arity;
+  }
+  unsigned log_gmax = (unsigned)(lb + prm.log_final_poly_len);
+  for (unsigned a : arities) {
+    if (a > prm.max_log_arity) return COLLECT_REFUSED;
+    log_gmax += a;
+  }
+  if (log_gmax > BB_TWO_ADICITY) return COLLECT_REFUSED;
+  std::vector<E4> betas;
+  for (size_t i = 0; i < nrounds; i++) {
+    ch.observe_cap(proof.commits[i]);
+    if (!check_witness(ch, (unsigned)prm.commit_pow_bits, proof.pow[i])) return COLLECT_REFUSED;
+    betas.push_back(ch.sample_e4());
+  }
+  if (proof.final_poly.size() != (size_t(1) << prm.log_final_poly_len)) return COLLECT_REFUSED;
+  for (auto& c : proof.final_poly) ch.observe_e4(c);
+  if (proof.queries.size() != prm.num_queries) return COLLECT_REFUSED;
+  if (!check_witness(ch, (unsigned)prm.query_pow_bits, proof.query_pow)) return COLLECT_REFUSED;
+  const unsigned log_final_height = (unsigned)(lb + prm.log_final_poly_len);
+  const size_t nq = proof.queries.size(), R = rounds.size();
+  if (nq == 0) return COLLECT_QUEUED;  // nothing is queried: pcs_verify accepts here as well (the flag stays clear)
+  std::vector<size_t> index(nq);
+  for (size_t q = 0; q < nq; q++) index[q] = ch.sample_bits(log_gmax);
+
+  // ---- the input rounds' structure, from the first query
+  struct RoundPlan {
+    PathPlan pl;
+    unsigned log_bmax = 0;
+    std::vector<size_t> width, row_off;  // per matrix: words, and where its row lies in a query's block
+    size_t words = 0, path_len = 0;
+  };
+  std::vector<RoundPlan> rp(R);
+  const VQuery& q0 = proof.queries[0];
+  if (q0.inputs.size() != R) return COLLECT_REFUSED;
+  size_t blk = 1;  // word 0 of a query's block is its index
+  std::map<unsigned, std::vector<std::pair<size_t, size_t>>, std::greater<unsigned>> by_height;  // (round, matrix) in ro's order
+  for (size_t ri = 0; ri < R; ri++) {
+    const RoundClaim& r = rounds[ri];
+    const VBatchOpening& bo = q0.inputs[ri];
+    RoundPlan& P = rp[ri];
+    if (bo.rows.size() != r.mats.size()) return COLLECT_REFUSED;
+    std::vector<Dim> dims;
+    for (size_t mi = 0; mi < r.mats.size(); mi++) {
+      dims.push_back(Dim{bo.rows[mi].size(), size_t(1) << (r.log_n[mi] + lb)});
+      P.log_bmax = std::max(P.log_bmax, r.log_n[mi] + lb);
+      P.width.push_back(bo.rows[mi].size());
+      for (auto& pv : r.mats[mi])
+        if (pv.second->size() != bo.rows[mi].size()) return COLLECT_REFUSED;
+      by_height[r.log_n[mi] + lb].push_back({ri, mi});
+    }
+    if (P.log_bmax > log_gmax) return COLLECT_REFUSED;
+    P.path_len = bo.path.size();
+    if (!mmcs_plan(dims, r.commit.size(), P.path_len, P.pl)) return COLLECT_REFUSED;
+    P.row_off.resize(dims.size());
+    for (size_t i : P.pl.order) {
+      P.row_off[i] = blk + P.words;
+      P.words += dims[i].w;
+    }
+    blk += P.words;
+  }
+  // ---- heights of the reduced openings, descending, and the fold chain's schedule
+  std::vector<unsigned> hs;
+  for (auto& kv : by_height) hs.push_back(kv.first);
+  const bool zero_rule = by_height.count(lb) && log_final_height >= lb && lb < log_gmax;  // lb is the lowest height: the last slot
+  const size_t n_chain = hs.size() - (zero_rule ? 1 : 0);
+  if (n_chain == 0 || hs[0] != log_gmax) return COLLECT_REFUSED;
+  struct StepPlan {
+    PathPlan pl;
+    size_t path_len = 0, row_off = 0, sib_off = 0;
+    unsigned shift = 0;  // the round's row index is the query index >> shift
+  };
+  std::vector<StepPlan> sp(nrounds);
+  size_t fri_stride = 0, sib_stride = 0;
+  {
+    size_t hp = 1;
+    unsigned lh = log_gmax, shift = 0;
+    for (size_t i = 0; i < nrounds; i++) {
+      const unsigned la = arities[i];
+      if (lh <= log_final_height) return COLLECT_REFUSED;
+      unsigned want = std::min<unsigned>((unsigned)prm.max_log_arity, lh - log_final_height);
+      if (hp < n_chain) want = std::min(want, lh - hs[hp]);
+      if (la != want) return COLLECT_REFUSED;
+      lh -= la;
+      shift += la;
+      const size_t m = size_t(1) << la;
+      sp[i].path_len = q0.steps[i].path.size();
+      sp[i].shift = shift;
+      sp[i].row_off = fri_stride;
+      sp[i].sib_off = sib_stride;
+      if (!mmcs_plan({Dim{4 * m, size_t(1) << lh}}, proof.commits[i].size(), sp[i].path_len, sp[i].pl)) return COLLECT_REFUSED;
+      fri_stride += 4 * m;
+      sib_stride += m - 1;
+      if (hp < n_chain && hs[hp] == lh) hp++;
+    }
+    if (hp != n_chain) return COLLECT_REFUSED;
+  }
+  // ---- every query has that structure
+  for (auto& qp : proof.queries) {
+    if (qp.inputs.size() != R || qp.steps.size() != nrounds) return COLLECT_REFUSED;
+    for (size_t ri = 0; ri < R; ri++) {
+      const VBatchOpening& bo = qp.inputs[ri];
+      if (bo.rows.size() != rp[ri].width.size()) return COLLECT_REFUSED;
+      for (size_t mi = 0; mi < bo.rows.size(); mi++)
+        if (bo.rows[mi].size() != rp[ri].width[mi]) return rounds[ri].mats[mi].empty() ? COLLECT_HOST : COLLECT_REFUSED;
+      if (bo.path.size() != rp[ri].path_len) return COLLECT_REFUSED;
+    }
+    for (size_t i = 0; i < nrounds; i++) {
+      const VFriStep& st = qp.steps[i];
+      if (st.log_arity != arities[i] || st.siblings.size() != (size_t(1) << arities[i]) - 1 || st.path.size() != sp[i].path_len) return COLLECT_REFUSED;
+    }
+  }
+
+  // ---- accepted so far: append
+  BVProofDesc D;
+  memset(&D, 0, sizeof(D));
+  D.alpha = alpha;
+  D.blk_off = B.words.size();
+  D.blk_stride = blk;
+  D.fri_off = B.fri_words;  // (bvbatch_seal adds the uploaded words in front)
+  D.fri_stride = fri_stride;
+  D.ro_off = B.ro_count;
+  D.sib_stride = (u32)sib_stride;
+  D.n_rounds = (u32)nrounds;
+  D.log_gmax = log_gmax;
+  D.query0 = (u32)B.qmap.size();
+  D.flag = flag;
+  D.n_heights = (u32)hs.size();
+  D.zero_slot = zero_rule ? (u32)(hs.size() - 1) : ~u32(0);
+  D.height_off = (u32)B.heights.size();
+  for (unsigned lh : hs) {
+    auto& list = by_height[lh];
+    BVHeightDesc H;
+    H.lh = lh;
+    H.mat_off = (u32)B.mats.size();
+    H.n_mats = (u32)list.size();
+    H.pad = 0;
+    B.heights.push_back(H);
+    for (auto& rm : list) {
+      const auto& pts = rounds[rm.first].mats[rm.second];
+      BVMatDesc M;
+      M.row_off = (u32)rp[rm.first].row_off[rm.second];
+      M.width = (u32)rp[rm.first].width[rm.second];
+      M.n_points = (u32)pts.size();
+      M.pv_off = (u32)B.ext.size();
+      B.mats.push_back(M);
+      for (auto& pv : pts) {
+        B.ext.push_back(pv.first);
+        B.ext.insert(B.ext.end(), pv.second->begin(), pv.second->end());
+      }
+    }
+  }
+  D.beta_off = (u32)B.ext.size();
+  B.ext.insert(B.ext.end(), betas.begin(), betas.end());
+  D.final_off = (u32)B.ext.size();
+  D.n_final = (u32)proof.final_poly.size();
+  B.ext.insert(B.ext.end(), proof.final_poly.begin(), proof.final_poly.end());
+  D.arity_off = (u32)B.u32s.size();
+  for (unsigned a : arities) B.u32s.push_back(a);
+  std::vector<u32> grp_in(R), cap_in(R), grp_fri(nrounds), cap_fri(nrounds);
+  for (size_t ri = 0; ri < R; ri++) {
+    grp_in[ri] = (u32)B.u32s.size();
+    B.u32s.insert(B.u32s.end(), rp[ri].pl.groups.begin(), rp[ri].pl.groups.end());
+    cap_in[ri] = (u32)B.digs.size();
+    B.digs.insert(B.digs.end(), rounds[ri].commit.begin(), rounds[ri].commit.end());
+  }
+  for (size_t i = 0; i < nrounds; i++) {
+    grp_fri[i] = (u32)B.u32s.size();
+    B.u32s.insert(B.u32s.end(), sp[i].pl.groups.begin(), sp[i].pl.groups.end());
+    cap_fri[i] = (u32)B.digs.size();
+    B.digs.insert(B.digs.end(), proof.commits[i].begin(), proof.commits[i].end());
+  }
+  D.sib_off = (u32)B.ext.size();
+  const u32 proof_slot = (u32)B.proofs.size();
+  for (size_t q = 0; q < nq; q++) {
+    const VQuery& qp = proof.queries[q];
+    B.words.push_back((u32)index[q]);
+    for (size_t ri = 0; ri < R; ri++) {
+      const VBatchOpening& bo = qp.inputs[ri];
+      const u64 vals_off = B.words.size();
+      for (size_t i : rp[ri].pl.order) B.words.insert(B.words.end(), bo.rows[i].begin(), bo.rows[i].end());
+      const u32 sib = (u32)B.digs.size();
+      B.digs.insert(B.digs.end(), bo.path.begin(), bo.path.end());
+      bv_add_item(B, rp[ri].pl, vals_off, false, index[q] >> (log_gmax - rp[ri].log_bmax), sib, cap_in[ri], grp_in[ri], flag);
+    }
+    for (size_t i = 0; i < nrounds; i++) {
+      const VFriStep& st = qp.steps[i];
+      B.ext.insert(B.ext.end(), st.siblings.begin(), st.siblings.end());
+      const u32 sib = (u32)B.digs.size();
+      B.digs.insert(B.digs.end(), st.path.begin(), st.path.end());
+      bv_add_item(B, sp[i].pl, B.fri_words + q * fri_stride + sp[i].row_off, true, index[q] >> sp[i].shift, sib, cap_fri[i], grp_fri[i], flag);
+    }
+    B.qmap.push_back(proof_slot);
+  }
+  B.fri_words += nq * fri_stride;
+  B.ro_count += nq * hs.size();
+  B.proofs.push_back(D);
+  return COLLECT_QUEUED;
+}
+
+}  // namespace
+
+void verify_batch(BSystem& sys, size_t n_proofs, const u64* n_claims, const u64* const* claim_offsets, const u32* const* claim_data,
+                  const uint8_t* const* proofs, const u64* proof_lens, int32_t* verdicts) {
+  Ctx& ctx = *sys.ctx;
+  HIP_CHECK(hipSetDevice(ctx.device));
+  static const u64 no_offsets[1] = {0};
+  BVBatch B;
+  std::vector<std::pair<size_t, int>> waiting;  // (proof, its out-of-domain verdict): the device decides between that and 2
+  std::vector<u32> fail;
+  auto flush = [&]() {
+    B.n_flags = waiting.size();
+    bvbatch_run(ctx, sys.d_perm.p, B, fail);
+    for (size_t k = 0; k < waiting.size(); k++) verdicts[waiting[k].first] = fail[k] ? V_INVALID_OPENING : waiting[k].second;
+    waiting.clear();
+    B = BVBatch();
+  };
+  for (size_t i = 0; i < n_proofs; i++) {
+    const u64* offs = n_claims[i] ? claim_offsets[i] : no_offsets;
+    Prepared P(&sys.perm);
+    const int v = verify_prepare(sys, (size_t)n_claims[i], offs, claim_data ? claim_data[i] : nullptr, proofs[i], (size_t)proof_lens[i], P);
+    if (v != V_OK) {
+      verdicts[i] = v;
+      continue;
+    }
+    const Challenger at_pcs = P.ch;
+    const int c = pcs_collect(sys, P.rounds, P.proof, P.ch, B, (u32)waiting.size());
+    if (c == COLLECT_HOST) {
+      Challenger ch = at_pcs;
+      verdicts[i] = pcs_verify(sys, P.rounds, P.proof, ch) ? verify_ood(sys, P) : V_INVALID_OPENING;
+      continue;
+    }
+    if (c == COLLECT_REFUSED) {
+      verdicts[i] = V_INVALID_OPENING;
+      continue;
+    }
+    waiting.push_back({i, verify_ood(sys, P)});
+    if (B.bytes() > BV_FLUSH_BYTES) flush();
+  }
+  flush();
+}
+
+// MerkleTreeMmcs::verify_batch for many openings of one commitment, one device thread per opening; everything canonical
+void mmcs_verify_batch_device(Ctx& ctx, const Poseidon2* d_perm, const std::vector<size_t>& heights, const std::vector<size_t>& widths,
+                              const u32* cap, unsigned cap_height, size_t n_openings, const u64* indices, const u32* vals, const u32* siblings,
+                              uint8_t* ok_out) {
+  HIP_CHECK(hipSetDevice(ctx.device));
+  if (n_openings == 0) return;
+  std::vector<Dim> dims;
+  size_t max_h = 0, row_words = 0;
+  for (size_t i = 0; i < heights.size(); i++) {
+    if (heights[i] == 0 || (heights[i] & (heights[i] - 1))) throw std::runtime_error("height must be a power of two");
+    dims.push_back(Dim{widths[i], heights[i]});
+    max_h = std::max(max_h, heights[i]);
+    row_words += widths[i];
+  }
+  if (dims.empty()) throw std::runtime_error("msbb_mmcs_verify_batch: no matrices");
+  const unsigned log_max = log2_strict(max_h);
+  if (cap_height > log_max) throw std::runtime_error("msbb_mmcs_verify_batch: cap_height above log2 of the tallest matrix");
+  const size_t path_len = log_max - cap_height, capn = size_t(1) << cap_height;
+  bool cap_ok = true;
+  for (size_t c = 0; c < 8 * capn; c++) cap_ok = cap_ok && cap[c] < BB_P;
+  PathPlan pl;
+  if (!cap_ok || !mmcs_plan(dims, capn, path_len, pl)) {  // a non-canonical cap equals no digest; a matrix shorter than the cap layer is
+    memset(ok_out, 0, n_openings);                        // never reached by the walk: MerkleTreeMmcs refuses every opening
+    return;
+  }
+  std::vector<size_t> col0(dims.size());  // where each matrix's row starts in an opening's values
+  for (size_t i = 0, at = 0; i < dims.size(); i++) col0[i] = at, at += dims[i].w;
+  auto canonical = [&](size_t k) {
+    bool ok = indices[k] < max_h;
+    const u32* v = vals + k * row_words;
+    for (size_t c = 0; c < row_words && ok; c++) ok = v[c] < BB_P;
+    const u32* s = siblings + k * path_len * 8;
+    for (size_t c = 0; c < path_len * 8 && ok; c++) ok = s[c] < BB_P;
+    return ok;
+  };
+  std::vector<u32> fail;
+  size_t k0 = 0;
+  while (k0 < n_openings) {
+    BVBatch B;
+    const u32 cap_off = 0, grp_off = 0;
+    B.digs.resize(capn);
+    for (size_t c = 0; c < 8 * capn; c++) B.digs[c / 8].w[c % 8] = bb_to_monty(cap[c]);
+    B.u32s = pl.groups;
+    size_t k = k0;
+    for (; k < n_openings && B.bytes() <= BV_FLUSH_BYTES; k++) {
+      if (!canonical(k)) continue;  // refused here; ok_out is set below
+      const u32* v = vals + k * row_words;
+      const u64 vals_off = B.words.size();
+      for (size_t i : pl.order)
+        for (size_t c = 0; c < dims[i].w; c++) B.words.push_back(bb_to_monty(v[col0[i] + c]));
+      const u32 sib = (u32)B.digs.size();
+      B.digs.resize(sib + path_len);
+      const u32* s = siblings + k * path_len * 8;
+      for (size_t c = 0; c < path_len * 8; c++) B.digs[sib + c / 8].w[c % 8] = bb_to_monty(s[c]);
+      bv_add_item(B, pl, vals_off, false, indices[k], sib, cap_off, grp_off, (u32)(k - k0));
+    }
+    B.n_flags = k - k0;
+    bvbatch_run(ctx, d_perm, B, fail);
+    for (size_t j = k0; j < k; j++) ok_out[j] = canonical(j) && !fail[j - k0] ? 1 : 0;
+    k0 = k;
+  }
 }
 
 }  // namespace msbb
@@ -1859,6 +2367,24 @@ int32_t msbb_verify(msbb_system* sys, size_t n_claims, const uint64_t* claim_off
   BB_CATCH
 }
 
+int32_t msbb_verify_batch(msbb_system* sys, size_t n_proofs, const uint64_t* n_claims, const uint64_t* const* claim_offsets,
+                          const uint32_t* const* claim_data, const uint8_t* const* proofs, const uint64_t* proof_lens, int32_t* verdicts) {
+  BB_TRY
+  if (n_proofs == 0) return MS_OK;
+  if (!sys || !verdicts || !proofs || !proof_lens || !n_claims) throw std::runtime_error("msbb_verify_batch: null argument");
+  for (size_t i = 0; i < n_proofs; i++) {
+    if (!proofs[i]) throw std::runtime_error("msbb_verify_batch: null proof");
+    if (n_claims[i]) {
+      if (!claim_offsets || !claim_offsets[i] || !claim_data) throw std::runtime_error("msbb_verify_batch: null claims");
+      // (an inconsistent offset table is a verdict; the data pointer is only needed where it says there are elements)
+      if (claim_offsets[i][n_claims[i]] && !claim_data[i]) throw std::runtime_error("msbb_verify_batch: null claims");
+    }
+  }
+  verify_batch(*sys->sys, n_proofs, n_claims, claim_offsets, claim_data, proofs, proof_lens, verdicts);
+  return MS_OK;
+  BB_CATCH
+}
+
 // ---- PCS-level entry points
 int32_t msbb_set_poseidon2(ms_ctx* ctx, const uint32_t* k141) {
   BB_TRY
@@ -1984,6 +2510,20 @@ int32_t msbb_mmcs_open(msbb_mmcs* m, size_t index, uint32_t* vals_out, uint32_t*
   for (u32 k = 0; k < vals; k++) vals_out[k] = bb_from_monty(g[k]);
   for (u32 k = vals; k < pos; k++) proof_out[k - vals] = bb_from_monty(g[k]);
   *n_siblings = log_max - ch_eff;
+  return MS_OK;
+  BB_CATCH
+}
+int32_t msbb_mmcs_verify_batch(ms_ctx* ctx, size_t n_mats, const uint64_t* heights, const uint64_t* widths, const uint32_t* cap,
+                               uint32_t cap_height, size_t n_openings, const uint64_t* indices, const uint32_t* vals, const uint32_t* siblings,
+                               uint8_t* ok_out) {
+  BB_TRY
+  if (n_openings == 0) return MS_OK;
+  if (!ctx || !heights || !widths || !cap || !indices || !vals || !siblings || !ok_out) throw std::runtime_error("msbb_mmcs_verify_batch: null argument");
+  Ctx& c = *msamd::ctx_of(ctx);
+  HIP_CHECK(hipSetDevice(c.device));
+  const Poseidon2* perm = need_perm(c);
+  std::vector<size_t> hs(heights, heights + n_mats), ws(widths, widths + n_mats);
+  mmcs_verify_batch_device(c, perm, hs, ws, cap, cap_height, n_openings, indices, vals, siblings, ok_out);
   return MS_OK;
   BB_CATCH
 }

@@ -5,7 +5,10 @@ verified N = 1, 8, 64 times per call, as a loop of System.verify and as one Syst
 of REPS timed repetitions after a warm-up, proofs/s, the GPU time of the batch's two launches (ms_ctx_kernel_stats, taken in a
 separate profiled pass) and the share of the batch call that is not kernel time (host part, upload, read-back).
 
-usage: python3 tools/verify_bench.py [--reps 10] [--logs 16,20] [--batches 1,8,64] [--json]"""
+--config babybear: the same comparison for the second configuration (msbb_verify / msbb_verify_batch, BabyBear / Poseidon2),
+on the u32_add + byte table workload at the bench parameters; --logs defaults to 12,16 there.
+
+usage: python3 tools/verify_bench.py [--config goldilocks|babybear] [--reps 10] [--logs 16,20] [--batches 1,8,64] [--json]"""
 import argparse
 import json
 import os
@@ -31,7 +34,8 @@ def _median_ms(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--logs", default="16,20")
+    ap.add_argument("--config", choices=["goldilocks", "babybear"], default="goldilocks")
+    ap.add_argument("--logs", default=None)
     ap.add_argument("--batches", default="1,8,64")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
@@ -39,11 +43,22 @@ def main():
     pkg = load_package()
     fe = pkg.frontend
     ctx = pkg.Context(0)
-    g = pkg.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs())
+    babybear = a.config == "babybear"
+    names = ("msbb_verify", "msbb_verify_batch") if babybear else ("ms_verify", "ms_verify_batch")
+    if babybear:
+        with fe.field(fe.BABYBEAR):
+            g = pkg.babybear.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs(), fe.poseidon2_constants())
+    else:
+        g = pkg.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs())
     rows = []
-    for log_n in [int(x) for x in a.logs.split(",")]:
-        traces, claims = fe.u32_add_bench_witness(1 << log_n)
-        packed = fe.pack_claims(claims)
+    for log_n in [int(x) for x in (a.logs or ("12,16" if babybear else "16,20")).split(",")]:
+        if babybear:
+            with fe.field(fe.BABYBEAR):
+                traces, claims = fe.u32_add_bench_witness(1 << log_n)
+                packed = fe.pack_claims(claims)
+        else:
+            traces, claims = fe.u32_add_bench_witness(1 << log_n)
+            packed = fe.pack_claims(claims)
         proof = g.prove_multiple_claims(g.witness(traces, packed)).to_bytes()
         assert g.verify(packed, proof) == 0
         for n in [int(x) for x in a.batches.split(",")]:
@@ -71,7 +86,7 @@ def main():
     if a.json:
         print(json.dumps(rows))
         return
-    print("| additions | proof bytes | batch | loop of ms_verify: ms (proofs/s) | ms_verify_batch: ms (proofs/s) | GPU kernels ms (paths) | not kernel time |")
+    print("| additions | proof bytes | batch | loop of %s: ms (proofs/s) | %s: ms (proofs/s) | GPU kernels ms (paths) | not kernel time |" % names)
     print("|---|---|---|---|---|---|---|")
     for r in rows:
         print("| 2^%d | %d | %d | %.2f (%.0f) | %.2f (%.0f) | %.3f (%.3f) | %.0f %% |" % (
