@@ -105,6 +105,10 @@ extern "C" {
                                          head: *const u64, n_head: usize, pinned: *mut i32, out: *mut *mut ms_witness) -> i32;
     pub fn ms_witness_prefetch(w: *mut ms_witness, on: i32) -> i32;
     pub fn ms_witness_u32_add_bench(sys: *mut ms_system, num_adds: usize, a0: u32, b0: u32, out: *mut *mut ms_witness) -> i32;
+    pub fn ms_witness_blake3_compressions(sys: *mut ms_system, n: usize, states_in: *const u32, states_out: *mut u32,
+                                          out: *mut *mut ms_witness) -> i32;
+    pub fn ms_blake3_compressions(data: *const u8, len: usize, states_in: *mut u32, cap_rows: usize, n: *mut usize, digest32: *mut u8) -> i32;
+    pub fn ms_witness_trace(w: *mut ms_witness, circuit: usize, out: *mut u64, cap_words: usize, n_words: *mut usize) -> i32;
     pub fn ms_witness_destroy(w: *mut ms_witness);
     pub fn ms_prove(sys: *mut ms_system, w: *mut ms_witness, proof_out: *mut u8, cap: usize, proof_len: *mut usize, stage_ms: *mut f64) -> i32;
     pub fn ms_verify(sys: *mut ms_system, n_claims: usize, claim_offsets: *const u64, claim_data: *const u64, proof: *const u8,

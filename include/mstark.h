@@ -148,6 +148,18 @@ int32_t ms_witness_prefetch(ms_witness* w, int32_t on);
  * build_claims of benches/multi_stark.rs:171-238 (two xorshift32 streams from a0, b0; the reference uses 0xdeadbeef,
  * 0xcafebabe) followed by from_stage_1 on the device. Nothing crosses PCIe. */
 int32_t ms_witness_u32_add_bench(ms_system* sys, size_t num_adds, uint32_t a0, uint32_t b0, ms_witness** out);
+/* Blake3CompressionClaims::witness (src/test_circuits/blake3.rs:1511-2213) on the device, for n claims of the compression
+ * circuit. states_in: n x 32 words [cv 8 | 4 words | counter lo, hi | block_len | flags | message 16] (any values: the circuit
+ * does not constrain words 8..11). The nine stage-1 traces, the claims [9, state_in 32, state_out 16] and from_stage_1 are
+ * produced in HBM; only the n x 32 input words cross PCIe. states_out (nullable): n x 16 output words. The system must be
+ * the nine-circuit BLAKE3 system (checked by shape); n = 0, or an n whose tallest trace exceeds the supported height: MS_ERR. */
+int32_t ms_witness_blake3_compressions(ms_system* sys, size_t n, const uint32_t* states_in, uint32_t* states_out, ms_witness** out);
+/* Host code, no device: every compression of BLAKE3(data) in the order of blake3_new_update_finalize (:32-352), as states_in
+ * rows for the call above. MS_ERR_BUFFER with *n = needed rows if cap_rows is too small. digest32 nullable. */
+int32_t ms_blake3_compressions(const uint8_t* data, size_t len, uint32_t* states_in, size_t cap_rows, size_t* n, uint8_t* digest32);
+/* Diagnostics: read back one stage-1 trace (height x main_width, row-major) of a device-resident witness.
+ * MS_ERR_BUFFER with *n_words = needed size. Host-resident witnesses: MS_ERR. */
+int32_t ms_witness_trace(ms_witness* w, size_t circuit, uint64_t* out, size_t cap_words, size_t* n_words);
 void ms_witness_destroy(ms_witness* w);
 
 /* ---- System::prove_multiple_claims (src/prover.rs:290-603). Writes Proof::to_bytes (src/prover.rs:241-248).

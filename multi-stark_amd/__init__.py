@@ -44,7 +44,7 @@ def exported_symbols():
     return ["ms_last_error", "ms_device_count", "ms_ctx_create", "ms_ctx_destroy", "ms_ctx_sync", "ms_ctx_sync_count", "ms_ctx_trim", "ms_ctx_set_profile_mask",
             "ms_ctx_kernel_stats", "ms_ctx_kernel_units", "ms_ctx_reset_stats", "ms_ctx_debug_fail_alloc", "ms_kernel_count", "ms_kernel_name", "ms_system_create",
             "ms_system_destroy", "ms_system_preprocessed_commit", "ms_system_circuit_info", "ms_system_circuit_kernels", "ms_witness_create", "ms_witness_create_host", "ms_claims_slice_range", "ms_witness_create_host_sliced", "ms_witness_prefetch",
-            "ms_witness_u32_add_bench", "ms_witness_destroy", "ms_prove", "ms_prove_sharded", "ms_ctx_comm_progress", "ms_comm_rccl_unique_id", "ms_comm_rccl_create",
+            "ms_witness_u32_add_bench", "ms_witness_blake3_compressions", "ms_blake3_compressions", "ms_witness_trace", "ms_witness_destroy", "ms_prove", "ms_prove_sharded", "ms_ctx_comm_progress", "ms_comm_rccl_unique_id", "ms_comm_rccl_create",
             "ms_comm_rccl_table", "ms_comm_rccl_bytes_moved", "ms_comm_rccl_destroy", "ms_comm_local_group_create", "ms_comm_local_group_abort",
             "ms_comm_local_group_destroy", "ms_comm_local_create", "ms_comm_local_table", "ms_comm_local_bytes_moved", "ms_comm_local_destroy", "ms_verify", "ms_verify_batch", "ms_dft_batch", "ms_coset_lde_batch", "ms_quotient_lde", "ms_mmcs_commit",
             "ms_mmcs_open", "ms_mmcs_destroy", "ms_mmcs_verify_batch", "ms_blake3", "ms_pcs_commit", "ms_pcs_open", "ms_pcs_verify", "ms_challenger_create",
@@ -451,6 +451,18 @@ class SystemWitness:
         """host-resident witness: every proof also uploads the inputs of the next one while it computes (ms_witness_prefetch)"""
         _check(lib().ms_witness_prefetch(self.h, C.c_int32(1 if on else 0)))
 
+    def trace(self, circuit):
+        """one stage-1 trace of a device-resident witness read back (ms_witness_trace): height x main_width, uint64"""
+        need = C.c_size_t()
+        rc = lib().ms_witness_trace(self.h, C.c_size_t(circuit), None, C.c_size_t(0), C.byref(need))
+        if rc != -3:
+            _check(rc)
+        width = self.system.circuit_info(circuit)["main_width"]
+        out = np.zeros((need.value // width, width), dtype=np.uint64)
+        if need.value:
+            _check(lib().ms_witness_trace(self.h, C.c_size_t(circuit), _p(out), C.c_size_t(out.size), C.byref(need)))
+        return out
+
     # ---- Level 2 (include/mstark.h): the prover's steps one by one, everything staying on the device
     def commit_stage1(self, heights, widths):
         """pcs.commit of the stage-1 traces (src/prover.rs:338-350); heights / widths of the ACTIVE circuits"""
@@ -602,6 +614,23 @@ class System:
         _check(lib().ms_witness_u32_add_bench(self.h, C.c_size_t(num_adds), C.c_uint32(a0), C.c_uint32(b0), C.byref(h)))
         height = max(1, 1 << (num_adds - 1).bit_length())
         return SystemWitness(h, 256 + height, self)
+
+    def blake3_witness_on_device(self, states_in):
+        """`Blake3CompressionClaims::witness` generated in HBM (ms_witness_blake3_compressions) for the nine-circuit BLAKE3 system
+        of blake3_circuit.py: states_in is n x 32 words, one compression per row (blake3_circuit.compression_states). The
+        witness carries the claims [9, state_in, state_out]; its `states_out` is the n x 16 array of output words."""
+        st = np.ascontiguousarray(states_in, dtype=np.uint32)
+        if st.ndim != 2 or st.shape[1] != 32:
+            raise MstarkError("states_in: expected n x 32 words")
+        n = st.shape[0]
+        out = np.zeros((max(n, 1), 16), dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        h = C.c_void_p()
+        _check(lib().ms_witness_blake3_compressions(self.h, C.c_size_t(n), st.ctypes.data_as(u32p), out.ctypes.data_as(u32p), C.byref(h)))
+        H = 1 << (n - 1).bit_length()
+        w = SystemWitness(h, 65536 + (2 * 512 + 5 * 64 + 1) * H, self)
+        w.states_out = out[:n]
+        return w
 
     def _out_buffer(self):
         # one output buffer per system, reused: a fresh 2 MB array per proof costs an mmap and a page fault per 4 KB touched

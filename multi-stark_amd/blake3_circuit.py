@@ -109,6 +109,26 @@ def blake3_compressions(data: bytes):
     return infos, b"".join(w.to_bytes(4, "little") for w in out[:8])
 
 
+def compression_states(data: bytes):
+    """(states_in: n x 32 uint32, one row [cv 8 | IV 4 | counter lo, hi | block_len | flags | message 16] per compression of
+    BLAKE3(data) in the order of `blake3_compressions`; the 32-byte digest) from the library's host code (ms_blake3_compressions):
+    the rows `System.blake3_witness_on_device` takes."""
+    import ctypes as C
+
+    from . import MstarkError, lib
+
+    buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+    digest = np.zeros(32, dtype=np.uint8)
+    n = C.c_size_t()
+    u8p, u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    states = np.zeros((max(1, (len(data) + 63) // 64 + (len(data) + 1023) // 1024), 32), dtype=np.uint32)
+    rc = lib().ms_blake3_compressions(buf.ctypes.data_as(u8p), C.c_size_t(len(data)), states.ctypes.data_as(u32p), C.c_size_t(states.shape[0]),
+                                      C.byref(n), digest.ctypes.data_as(u8p))
+    if rc != 0:
+        raise MstarkError(lib().ms_last_error().decode() or "ms_blake3_compressions: %d" % rc)
+    return states[: n.value].copy(), digest.tobytes()
+
+
 def compression_claim(info):
     """[channel 9, state_in (32 words: cv, IV[..4], counter, block_len, flags, message), state_out (16 words)] (:2222-2239, :2319-2329)"""
     return [COMPRESSION] + info["cv"] + IV[:4] + [info["counter_low"], info["counter_high"], info["block_len"], info["flags"]] + \

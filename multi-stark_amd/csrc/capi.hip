@@ -312,6 +312,39 @@ int32_t ms_witness_u32_add_bench(ms_system* sys, size_t num_adds, uint32_t a0, u
   return MS_OK;
   MS_CATCH
 }
+int32_t ms_witness_blake3_compressions(ms_system* sys, size_t n, const uint32_t* states_in, uint32_t* states_out, ms_witness** out) {
+  *out = nullptr;
+  MS_TRY std::unique_ptr<ms_witness> w(new ms_witness());
+  w->w = witness_blake3_compressions(*sys->sys, n, states_in, states_out);
+  w->owner = sys;
+  sys->refs++;
+  *out = w.release();
+  return MS_OK;
+  MS_CATCH
+}
+int32_t ms_blake3_compressions(const uint8_t* data, size_t len, uint32_t* states_in, size_t cap_rows, size_t* n, uint8_t* digest32) {
+  MS_TRY if (!n || (len && !data) || (cap_rows && !states_in)) throw std::runtime_error("ms_blake3_compressions: null argument");
+  *n = blake3_compression_states(data, len, states_in, cap_rows, digest32);
+  return *n > cap_rows ? MS_ERR_BUFFER : MS_OK;
+  MS_CATCH
+}
+int32_t ms_witness_trace(ms_witness* w, size_t circuit, uint64_t* out, size_t cap_words, size_t* n_words) {
+  MS_TRY if (!w || !n_words) throw std::runtime_error("ms_witness_trace: null argument");
+  HWitness& wit = *w->w;
+  if (wit.host_resident) throw std::runtime_error("ms_witness_trace: a host-resident witness keeps its traces in the caller's buffers");
+  if (circuit >= wit.heights.size()) throw std::runtime_error("ms_witness_trace: no such circuit");
+  const size_t words = wit.heights[circuit] * wit.sys->circuits[circuit].main_width;
+  if (words && !wit.traces[circuit].p) throw std::runtime_error("ms_witness_trace: this circuit's trace is held by another rank");
+  *n_words = words;
+  if (words > cap_words) return MS_ERR_BUFFER;
+  if (!words) return MS_OK;
+  if (!out) throw std::runtime_error("ms_witness_trace: null output");
+  Ctx& ctx = *wit.sys->ctx;
+  HIP_CHECK(hipSetDevice(ctx.device));
+  ctx.d2h(out, wit.traces[circuit].p, words * 8);
+  return MS_OK;
+  MS_CATCH
+}
 void ms_witness_destroy(ms_witness* w) {
   if (!w) return;
   ms_system* s = w->owner;

@@ -157,10 +157,20 @@ std::unique_ptr<HWitness> witness_create(HSystem& sys, const u64* const* traces,
                                          const u64* const* args, size_t n_claims, const u64* claim_offsets,
                                          const u64* claim_data);
 
-// traces / claims already resident in HBM (from_stage_1 on the device); and the bench workload generated there
+// traces / claims already resident in HBM (from_stage_1 on the device); and the bench workload generated there.
+// ready (optional, one entry per circuit): LookupValues the generator already holds in HBM (mult: h x num_lookups, args:
+// h x args_width, as host_lookup_values lays them out); a circuit with an entry takes it as it is, the others run from_stage_1
+struct ReadyLookups {
+  DBuf<u64> mult, args;
+};
 std::unique_ptr<HWitness> witness_from_device(HSystem& sys, std::vector<DBuf<u64>>&& traces, const std::vector<size_t>& heights,
-                                              DBuf<u64>&& d_claim_offsets, DBuf<u64>&& d_claim_data, size_t n_claims, size_t claim_elems);
+                                              DBuf<u64>&& d_claim_offsets, DBuf<u64>&& d_claim_data, size_t n_claims, size_t claim_elems,
+                                              std::vector<ReadyLookups>* ready = nullptr);
 std::unique_ptr<HWitness> witness_u32_add_bench(HSystem& sys, size_t num_adds, u32 a0, u32 b0);
+// Blake3CompressionClaims::witness for the nine-circuit BLAKE3 system (witness_gen.hip); states_out nullable
+std::unique_ptr<HWitness> witness_blake3_compressions(HSystem& sys, size_t n, const u32* states_in, u32* states_out);
+// every compression of BLAKE3(data) as 32-word rows (host code); returns the number of rows, of which min(n, cap_rows) are written
+size_t blake3_compression_states(const uint8_t* data, size_t len, u32* states_in, size_t cap_rows, uint8_t* digest32);
 
 struct StageMs {
   double v[6] = {0, 0, 0, 0, 0, 0};

@@ -410,10 +410,12 @@ void host_lookup_values(const HCircuit& c, const u64* tr, size_t h, std::vector<
 
 // A witness whose traces and claims are already in HBM (witness_gen.hip): SystemWitness::from_stage_1 runs on the device.
 std::unique_ptr<HWitness> witness_from_device(HSystem& sys, std::vector<DBuf<u64>>&& traces, const std::vector<size_t>& heights,
-                                              DBuf<u64>&& d_claim_offsets, DBuf<u64>&& d_claim_data, size_t n_claims, size_t claim_elems) {
+                                              DBuf<u64>&& d_claim_offsets, DBuf<u64>&& d_claim_data, size_t n_claims, size_t claim_elems,
+                                              std::vector<ReadyLookups>* ready) {
   Ctx& ctx = *sys.ctx;
   const size_t C = sys.circuits.size();
   if (traces.size() != C || heights.size() != C) throw std::runtime_error("expected one trace per circuit");
+  if (ready && ready->size() != C) throw std::runtime_error("expected one (possibly empty) set of lookup values per circuit");
   std::unique_ptr<HWitness> w(new HWitness());
   w->sys = &sys;
   w->heights = heights;
@@ -436,6 +438,14 @@ std::unique_ptr<HWitness> witness_from_device(HSystem& sys, std::vector<DBuf<u64
     for (auto& l : c.lookups) offs.push_back(offs.back() + (uint32_t)l.second.size());
     lk.arg_offsets = DBuf<uint32_t>(ctx, offs.size());
     ctx.h2d(lk.arg_offsets.p, offs.data(), offs.size() * 4);
+    if (ready && (*ready)[ci].mult.p) {  // the generator wrote this circuit's LookupValues next to its trace
+      ReadyLookups& r = (*ready)[ci];
+      if (r.mult.n != h * c.num_lookups || r.args.n != std::max<size_t>(h * c.args_width, 1))
+        throw std::runtime_error("device-resident witness: ready-made lookup values of the wrong size");
+      lk.mult = std::move(r.mult);
+      lk.args = std::move(r.args);
+      continue;
+    }
     if (c.stage2_trace_jit.function && !getenv("MSAMD_MATERIALISE_LOOKUPS")) continue;  // stage 2 reads the trace itself
     lk.mult = DBuf<u64>(ctx, h * c.num_lookups);
     lk.args = DBuf<u64>(ctx, std::max<size_t>(h * c.args_width, 1));
