@@ -36,6 +36,22 @@ pub const MS_VERDICT_INVALID_SYSTEM: i32 = 4;
 pub const MS_VERDICT_OOD_MISMATCH: i32 = 5;
 pub const MS_VERDICT_UNBALANCED: i32 = 6;
 
+/// One stage-1 trace in device memory (ms_witness_create_device / msbb_witness_create_device): element (r, c) is the unsigned
+/// little-endian integer of `elem_bytes` bytes at `ptr + (r * row_stride + c * col_stride) * elem_bytes`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ms_dev_matrix {
+    /// null only with height 0 (inactive circuit)
+    pub ptr: *const c_void,
+    /// rows; the width is the circuit's main_width
+    pub height: u64,
+    /// 1, 2, 4 or 8 (msbb: 1, 2 or 4)
+    pub elem_bytes: u32,
+    /// in elements, both > 0
+    pub row_stride: i64,
+    pub col_stride: i64,
+}
+
 /// Exchanges `ms_prove_sharded` calls back for (device pointers of the context's device; 0 = ok).
 #[repr(C)]
 pub struct ms_comm {
@@ -104,6 +120,9 @@ extern "C" {
                                          claim_offsets: *const u64, data_first: u64, data_count: u64, data_slice: *const u64,
                                          head: *const u64, n_head: usize, pinned: *mut i32, out: *mut *mut ms_witness) -> i32;
     pub fn ms_witness_prefetch(w: *mut ms_witness, on: i32) -> i32;
+    pub fn ms_witness_create_device(sys: *mut ms_system, traces: *const ms_dev_matrix, n_claims: usize, claim_offsets: *const u64,
+                                    claim_data: *const u64, claims_on_device: i32, producer_stream: *mut c_void,
+                                    out: *mut *mut ms_witness) -> i32;
     pub fn ms_witness_u32_add_bench(sys: *mut ms_system, num_adds: usize, a0: u32, b0: u32, out: *mut *mut ms_witness) -> i32;
     pub fn ms_witness_blake3_compressions(sys: *mut ms_system, n: usize, states_in: *const u32, states_out: *mut u32,
                                           out: *mut *mut ms_witness) -> i32;
@@ -187,6 +206,8 @@ extern "C" {
                                claim_offsets: *const u64, claim_data: *const u32, out: *mut *mut msbb_witness) -> i32;
     pub fn msbb_witness_create_host(sys: *mut msbb_system, traces: *const *const u32, heights: *const u64, n_claims: usize,
                                     claim_offsets: *const u64, claim_data: *const u32, pinned: *mut i32, out: *mut *mut msbb_witness) -> i32;
+    pub fn msbb_witness_create_device(sys: *mut msbb_system, traces: *const ms_dev_matrix, n_claims: usize, claim_offsets: *const u64,
+                                      claim_data: *const u32, producer_stream: *mut c_void, out: *mut *mut msbb_witness) -> i32;
     pub fn msbb_witness_destroy(w: *mut msbb_witness);
     pub fn msbb_prove(sys: *mut msbb_system, w: *mut msbb_witness, proof_out: *mut u8, cap: usize, proof_len: *mut usize,
                       stage_ms: *mut f64) -> i32;

@@ -144,6 +144,47 @@ int32_t ms_witness_create_host(ms_system* sys, const uint64_t* const* traces, co
  * host buffers are fixed for the life of the witness anyway, see ms_witness_create_host.) bench.py reports this mode as
  * config.pipelined_ms_per_proof, never as the primary figure (whose every step starts with the witness in host memory). */
 int32_t ms_witness_prefetch(ms_witness* w, int32_t on);
+/* A SystemWitness whose stage-1 traces the CALLER holds in DEVICE memory - written there by its own kernels, by tensor
+ * operations or by another library. Nothing crosses PCIe: one launch per circuit reads the caller's matrix through its strides,
+ * checks every element against the field modulus and writes the witness's own copy; SystemWitness::from_stage_1 runs on the
+ * device. traces: one ms_dev_matrix per circuit; the width is the circuit's main_width; element (r, c) lies at
+ * ptr + (r * row_stride + c * col_stride) * elem_bytes and is an unsigned little-endian integer of elem_bytes bytes (row-major:
+ * strides (width, 1); column-major: (1, height); a column slice or padded rows: row_stride > width; every k-th row: row_stride =
+ * k * width). Only elements of the view are read or judged, never the padding between them.
+ *   Copy, not adoption: when the call returns - with any status - the library has finished reading the caller's buffers (traces
+ * and claims); they may be freed or overwritten. The result is an ordinary device-resident ms_witness: ms_prove,
+ * ms_witness_trace and the Level-2 calls (ms_witness_commit_stage1, ms_challenger_observe_claims, ms_stage2_build, ...) accept
+ * it. Circuits held by other ranks (ms_prove_sharded) cannot be expressed: a NULL pointer with height > 0 is MS_ERR.
+ *   Two limits. from_stage_1 must be able to run on the device: a circuit with lookups that has neither a generated stage-2
+ * kernel fed by the trace (MS_KERNEL_STAGE2_TRACE) nor a lookup prefix small enough for the device sweep is MS_ERR ("lookup
+ * prefix does not fit the device sweep"; ms_witness_create runs such a prefix on the host). And the memory must be an
+ * allocation the runtime can bound (hipMalloc and what tensor libraries carve out of it): a pointer for which
+ * hipMemGetAddressRange reports no base and size - virtual-memory mappings or stream-ordered pools on some runtimes - is
+ * refused rather than read unchecked.
+ *   Stream ordering: with producer_stream != NULL (a hipStream_t) the library records an event on that stream and makes its own
+ * stream wait for it before the first read, so the caller need not synchronise after queuing the work that fills the buffers.
+ * With NULL the caller has already made the data visible (or filled them on the null stream, which the library's stream
+ * follows).
+ *   Host waits: one per call on the traces' path, for the offender words, plus those of from_stage_1 and of the claims.
+ *   Refused on the host before anything is launched (MS_ERR, text via ms_last_error()): a pointer that hipPointerGetAttributes
+ * does not report as device memory of the context's device (host addresses, other devices), or whose view reaches beyond the
+ * allocation hipMemGetAddressRange reports around it; a pointer not aligned to elem_bytes; elem_bytes outside {1, 2, 4, 8}; a stride <= 0; height, width and strides
+ * whose product overflows; a height that is not a power of two or above the supported maximum; a height other than the
+ * circuit's preprocessed height; a NULL pointer with height > 0.
+ *   A value >= p (only 8-byte elements can be): MS_ERR naming the first offender in row-major order, e.g.
+ * "non-canonical trace value: circuit 1, row 5, column 3". The context stays usable.
+ *   Claims: with claims_on_device = 0 host arrays exactly as for ms_witness_create; with 1 both are device pointers to u64
+ * (same device, 8-byte aligned), read behind producer_stream as well. Either way offsets start at 0 and do not decrease and
+ * the data are canonical, else MS_ERR. */
+typedef struct ms_dev_matrix {      /* one trace in device memory of the system's context's device */
+  const void* ptr;                  /* NULL only with height 0 (inactive circuit) */
+  uint64_t height;                  /* rows; width is the circuit's main_width */
+  uint32_t elem_bytes;              /* 1, 2, 4, 8: unsigned little-endian */
+  int64_t row_stride, col_stride;   /* in elements; both > 0 */
+} ms_dev_matrix;
+int32_t ms_witness_create_device(ms_system* sys, const ms_dev_matrix* traces /* one per circuit */, size_t n_claims,
+                                 const uint64_t* claim_offsets, const uint64_t* claim_data, int32_t claims_on_device,
+                                 void* producer_stream /* hipStream_t, nullable */, ms_witness** out);
 /* The bench workload's witness and claims generated in HBM for the system [ByteTable, U32Add]: build_witness +
  * build_claims of benches/multi_stark.rs:171-238 (two xorshift32 streams from a0, b0; the reference uses 0xdeadbeef,
  * 0xcafebabe) followed by from_stage_1 on the device. Nothing crosses PCIe. */

@@ -56,6 +56,13 @@ int32_t msbb_witness_create(msbb_system* sys, const uint32_t* const* traces, con
 int32_t msbb_witness_create_host(msbb_system* sys, const uint32_t* const* traces, const uint64_t* heights, size_t n_claims,
                                  const uint64_t* claim_offsets, const uint32_t* claim_data, int32_t* pinned /* nullable */,
                                  msbb_witness** out);
+/* ms_witness_create_device for this configuration: the traces lie in device memory as ms_dev_matrix views (include/mstark.h)
+ * with elem_bytes 1, 2 or 4; a 4-byte value >= p is refused with its circuit, row and column; the library's copy is the
+ * column-major Montgomery matrix msbb_witness_create would have made. Same copy semantics, producer_stream ordering, single
+ * host wait on the traces' path and host-side refusals. Claims come from host memory, as for msbb_witness_create. */
+int32_t msbb_witness_create_device(msbb_system* sys, const ms_dev_matrix* traces /* one per circuit */, size_t n_claims,
+                                   const uint64_t* claim_offsets, const uint32_t* claim_data, void* producer_stream /* hipStream_t, nullable */,
+                                   msbb_witness** out);
 void msbb_witness_destroy(msbb_witness* w);
 
 /* Writes Proof::to_bytes (src/prover.rs:241-248). stage_ms (optional, 6 doubles) as for ms_prove. */

@@ -44,7 +44,7 @@ def exported_symbols():
     return ["ms_last_error", "ms_device_count", "ms_ctx_create", "ms_ctx_destroy", "ms_ctx_sync", "ms_ctx_sync_count", "ms_ctx_trim", "ms_ctx_set_profile_mask",
             "ms_ctx_kernel_stats", "ms_ctx_kernel_units", "ms_ctx_reset_stats", "ms_ctx_debug_fail_alloc", "ms_kernel_count", "ms_kernel_name", "ms_system_create",
             "ms_system_destroy", "ms_system_preprocessed_commit", "ms_system_circuit_info", "ms_system_circuit_kernels", "ms_witness_create", "ms_witness_create_host", "ms_claims_slice_range", "ms_witness_create_host_sliced", "ms_witness_prefetch",
-            "ms_witness_u32_add_bench", "ms_witness_blake3_compressions", "ms_blake3_compressions", "ms_witness_trace", "ms_witness_destroy", "ms_prove", "ms_prove_sharded", "ms_ctx_comm_progress", "ms_comm_rccl_unique_id", "ms_comm_rccl_create",
+            "ms_witness_create_device", "ms_witness_u32_add_bench", "ms_witness_blake3_compressions", "ms_blake3_compressions", "ms_witness_trace", "ms_witness_destroy", "ms_prove", "ms_prove_sharded", "ms_ctx_comm_progress", "ms_comm_rccl_unique_id", "ms_comm_rccl_create",
             "ms_comm_rccl_table", "ms_comm_rccl_bytes_moved", "ms_comm_rccl_destroy", "ms_comm_local_group_create", "ms_comm_local_group_abort",
             "ms_comm_local_group_destroy", "ms_comm_local_create", "ms_comm_local_table", "ms_comm_local_bytes_moved", "ms_comm_local_destroy", "ms_verify", "ms_verify_batch", "ms_dft_batch", "ms_coset_lde_batch", "ms_quotient_lde", "ms_mmcs_commit",
             "ms_mmcs_open", "ms_mmcs_destroy", "ms_mmcs_verify_batch", "ms_blake3", "ms_pcs_commit", "ms_pcs_open", "ms_pcs_verify", "ms_challenger_create",
@@ -79,6 +79,87 @@ def _b(a):
 
 def _u64(a):
     return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+class DevMatrix(C.Structure):
+    """ms_dev_matrix (include/mstark.h): one trace in device memory, strides in elements"""
+    _fields_ = [("ptr", C.c_void_p), ("height", C.c_uint64), ("elem_bytes", C.c_uint32), ("row_stride", C.c_int64), ("col_stride", C.c_int64)]
+
+
+def _is_torch(obj):
+    return type(obj).__module__.split(".")[0] == "torch" and hasattr(obj, "data_ptr")
+
+
+def _device_array(obj, what):
+    """(pointer, shape, strides in elements, element size, is a torch tensor) of a torch tensor on a GPU or of any object with
+    __cuda_array_interface__; MstarkError for anything that has no device pointer (numpy arrays, CPU tensors). The bits are
+    taken as unsigned integers of the element's size whatever the dtype."""
+    if _is_torch(obj):
+        if not obj.is_cuda:
+            raise MstarkError("%s: a CPU tensor has no device pointer (use System.witness)" % what)
+        return int(obj.data_ptr()), tuple(int(x) for x in obj.shape), tuple(int(x) for x in obj.stride()), int(obj.element_size()), True
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if cai is None:
+        raise MstarkError("%s: %s has no device pointer (expected a torch tensor on the GPU or __cuda_array_interface__)" % (what, type(obj).__name__))
+    shape = tuple(int(x) for x in cai["shape"])
+    item = np.dtype(cai["typestr"]).itemsize
+    strides = cai.get("strides")
+    if strides is None:  # C-contiguous
+        strides, acc = [], item
+        for n in reversed(shape):
+            strides.insert(0, acc)
+            acc *= max(n, 1)
+    if any(int(b) % item for b in strides):
+        raise MstarkError("%s: strides are not whole elements" % what)
+    return int(cai["data"][0] or 0), shape, tuple(int(b) // item for b in strides), item, False
+
+
+def _device_traces(traces, n_circuits, widths_of):
+    """the ms_dev_matrix array of witness_from_device (both configurations). widths_of(i) = main_width of circuit i, asked only
+    once every entry has been found to be 2-D device memory. -> (array, heights, the first torch tensor seen or None). Nothing is
+    kept alive: the library has finished reading the inputs when its call returns."""
+    if len(traces) != n_circuits:
+        raise MstarkError("expected one trace per circuit")
+    desc, seen_torch = [], None
+    for i, t in enumerate(traces):
+        what = "trace of circuit %d" % i
+        if t is None or (not _is_torch(t) and not hasattr(t, "__cuda_array_interface__") and hasattr(t, "__len__") and len(t) == 0):
+            desc.append(None)
+            continue
+        ptr, shape, strides, item, is_torch = _device_array(t, what)
+        if len(shape) != 2:
+            raise MstarkError("%s: expected a 2-D matrix, got %d dimension(s)" % (what, len(shape)))
+        if is_torch and seen_torch is None:
+            seen_torch = t
+        desc.append((ptr, shape, strides, item))
+    arr = (DevMatrix * max(n_circuits, 1))()
+    heights = []
+    for i, d in enumerate(desc):
+        if d is None or d[1][0] == 0:
+            arr[i] = DevMatrix(None, 0, 1, 1, 1)
+            heights.append(0)
+            continue
+        ptr, (h, w), (rs, cs), item = d
+        width = widths_of(i)
+        if w != width:
+            raise MstarkError("trace of circuit %d: width %d, the circuit's main_width is %d" % (i, w, width))
+        # an axis of one element has no stride to speak of
+        arr[i] = DevMatrix(ptr or None, h, item, rs if h > 1 else max(w, 1), cs if w > 1 else 1)
+        heights.append(h)
+    return arr, heights, seen_torch
+
+
+def _producer_stream(stream, torch_tensor):
+    """the producer_stream argument: an integer handle or an object with .cuda_stream passes through; None = the tensor
+    library's current stream when torch tensors were given (torch is imported only here), else NULL"""
+    if stream is None:
+        if torch_tensor is None:
+            return None
+        import torch
+
+        stream = torch.cuda.current_stream(torch_tensor.device)
+    handle = int(getattr(stream, "cuda_stream", stream))
+    return C.c_void_p(handle) if handle else None  # (0 is the null stream, which the library's own stream follows anyway)
 
 
 def device_count() -> int:
@@ -578,6 +659,35 @@ class System:
         w.keep = trs
         w.pinned = bool(pinned.value)
         return w
+
+    def witness_from_device(self, traces, claims_packed, stream=None):
+        """A SystemWitness from traces that already lie in DEVICE memory (ms_witness_create_device): nothing crosses PCIe, the
+        library checks and copies them with one launch per circuit. traces: per circuit None (inactive) or a 2-D torch tensor on
+        the context's device / any object with __cuda_array_interface__; shape, strides and element size (1, 2, 4 or 8 bytes,
+        read as unsigned: an int64 tensor carries u64 values) come from the object, so row-major, column-major, column slices
+        and row-step slices all work. claims_packed: the usual (offsets, data) numpy pair, or a pair of 1-D contiguous 64-bit
+        device arrays. stream: the stream that fills the inputs - None = torch's current stream when torch tensors are given
+        (no synchronisation needed), else the data must already be visible; or a hipStream_t handle as an integer. The inputs
+        may be overwritten or freed as soon as the call returns."""
+        arr, heights, seen = _device_traces(traces, self.n_circuits, lambda i: self.circuit_info(i)["main_width"])
+        offs, data = claims_packed
+        on_device = _is_torch(offs) or hasattr(offs, "__cuda_array_interface__")
+        if on_device:
+            po, so, sto, io, t_o = _device_array(offs, "claim offsets")
+            pd, sd, std, idt, t_d = _device_array(data, "claim data")
+            if len(so) != 1 or len(sd) != 1 or io != 8 or idt != 8 or (so[0] > 1 and sto[0] != 1) or (sd[0] > 1 and std[0] != 1) or so[0] < 1:
+                raise MstarkError("device claims: expected two 1-D contiguous arrays of 64-bit words (offsets, data)")
+            if seen is None and (t_o or t_d):
+                seen = offs if t_o else data
+            n_claims, poffs, pdata = so[0] - 1, C.c_void_p(po), C.c_void_p(pd or None)
+        else:
+            offs = _u64(offs)
+            data = _u64(data) if len(data) else np.zeros(1, dtype=np.uint64)
+            n_claims, poffs, pdata = len(offs) - 1, _p(offs), _p(data)
+        h = C.c_void_p()
+        _check(lib().ms_witness_create_device(self.h, arr, C.c_size_t(n_claims), poffs, pdata, C.c_int32(1 if on_device else 0),
+                                              _producer_stream(stream, seen), C.byref(h)))
+        return SystemWitness(h, int(sum(heights)), self)
 
     def claims_slice_range(self, heights, claim_offsets, rank, world):
         """(first element, count) of the claims' data that rank `rank` of `world` reads in a joint proof (ms_claims_slice_range)"""

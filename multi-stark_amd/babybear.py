@@ -18,7 +18,7 @@ P = frontend.BABYBEAR["P"]
 def exported_symbols():
     """Every entry point include/mstark_bb.h declares (used by the CPU-side ABI test)."""
     return ["msbb_system_create", "msbb_system_destroy", "msbb_system_preprocessed_commit", "msbb_system_circuit_info", "msbb_system_circuit_kernels",
-            "msbb_witness_create", "msbb_witness_create_host", "msbb_witness_destroy", "msbb_prove", "msbb_verify", "msbb_verify_batch", "msbb_set_poseidon2", "msbb_poseidon2_permute",
+            "msbb_witness_create", "msbb_witness_create_host", "msbb_witness_create_device", "msbb_witness_destroy", "msbb_prove", "msbb_verify", "msbb_verify_batch", "msbb_set_poseidon2", "msbb_poseidon2_permute",
             "msbb_dft_batch", "msbb_coset_lde_batch", "msbb_mmcs_commit", "msbb_mmcs_open", "msbb_mmcs_verify_batch", "msbb_mmcs_destroy", "msbb_field_op",
             "msbb_challenger_create", "msbb_challenger_destroy", "msbb_challenger_observe", "msbb_challenger_observe_digests",
             "msbb_challenger_sample_ext", "msbb_challenger_sample_bits", "msbb_challenger_observe_claims", "msbb_trace_destroy", "msbb_trace_info",
@@ -137,6 +137,22 @@ class System:
     def host_witness(self, traces, claims_packed):
         """a SystemWitness that stays in host memory: every prove_multiple_claims uploads it (msbb_witness_create_host)"""
         return Witness(self, traces, claims_packed, host_resident=True)
+
+    def witness_from_device(self, traces, claims_packed, stream=None):
+        """A witness from traces that already lie in DEVICE memory (msbb_witness_create_device): per circuit None (inactive) or a
+        2-D torch tensor on the context's device / any object with __cuda_array_interface__, of 1-, 2- or 4-byte elements read
+        as unsigned canonical values, in any strided layout. Claims: the usual (offsets, data) pair in host memory. stream as
+        for the Goldilocks System.witness_from_device. The inputs may be overwritten or freed as soon as the call returns."""
+        pkg = _pkg()
+        arr, _heights, seen = pkg._device_traces(traces, self.n_circuits, lambda i: self.circuit_info(i)["main_width"])
+        offs, data = claims_packed
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        data = _u32(data)
+        w = Witness.__new__(Witness)
+        w.system, w.h = self, C.c_void_p()
+        _check(_lib().msbb_witness_create_device(self.h, arr, C.c_size_t(len(offs) - 1), offs.ctypes.data_as(u64p), _p32(data),
+                                                 pkg._producer_stream(stream, seen), C.byref(w.h)))
+        return w
 
     def verify_multiple_claims(self, claims_packed, proof: bytes):
         """0 = accepted, otherwise the reference's VerificationError variant (MS_VERDICT_*)"""

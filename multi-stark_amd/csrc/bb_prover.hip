@@ -11,6 +11,7 @@
 #include "../../include/mstark_bb.h"
 #include "bb.h"
 #include "bb_verify_dev.h"
+#include "ingest.h"
 
 namespace msbb {
 
@@ -324,6 +325,28 @@ std::unique_ptr<BSystem> system_from_blob(Ctx& ctx, const uint8_t* blob, size_t 
   return sys;
 }
 
+// the claims of a device-resident witness: validated, kept canonical on the host (transcript) and uploaded in Montgomery form
+static void upload_claims(Ctx& ctx, BWitness& w, size_t n_claims, const u64* claim_offsets, const u32* claim_data) {
+  std::vector<u32> flat;
+  for (size_t i = 0; i < n_claims; i++) {
+    if (claim_offsets[i + 1] < claim_offsets[i]) throw std::runtime_error("claim offsets must not decrease");
+    w.claims.emplace_back(claim_data + claim_offsets[i], claim_data + claim_offsets[i + 1]);
+    for (u32 x : w.claims.back()) {
+      if (x >= BB_P) throw std::runtime_error("non-canonical claim value");
+      flat.push_back(bb_to_monty(x));
+    }
+  }
+  if (n_claims) {
+    std::vector<u64> offs(n_claims + 1);
+    for (size_t i = 0; i <= n_claims; i++) offs[i] = claim_offsets[i] - claim_offsets[0];
+    w.d_claim_offs = DBuf<u64>(ctx, n_claims + 1);
+    w.d_claim_data = DBuf<u32>(ctx, std::max<size_t>(flat.size(), 1));
+    ctx.h2d(w.d_claim_offs.p, offs.data(), offs.size() * 8);
+    if (!flat.empty()) ctx.h2d(w.d_claim_data.p, flat.data(), flat.size() * 4);
+    ctx.sync();
+  }
+}
+
 std::unique_ptr<BWitness> witness_create(BSystem& sys, const u32* const* traces, const u64* heights, size_t n_claims, const u64* claim_offsets,
                                          const u32* claim_data) {
   Ctx& ctx = *sys.ctx;
@@ -346,24 +369,56 @@ std::unique_ptr<BWitness> witness_create(BSystem& sys, const u32* const* traces,
       if (traces[ci][i] >= BB_P) throw std::runtime_error("non-canonical trace value");
     bb_upload_rows(ctx, traces[ci], h, c.main_width, w->traces.back());
   }
-  std::vector<u32> flat;
-  for (size_t i = 0; i < n_claims; i++) {
-    if (claim_offsets[i + 1] < claim_offsets[i]) throw std::runtime_error("claim offsets must not decrease");
-    w->claims.emplace_back(claim_data + claim_offsets[i], claim_data + claim_offsets[i + 1]);
-    for (u32 x : w->claims.back()) {
-      if (x >= BB_P) throw std::runtime_error("non-canonical claim value");
-      flat.push_back(bb_to_monty(x));
+  upload_claims(ctx, *w, n_claims, claim_offsets, claim_data);
+  return w;
+}
+
+// msbb_witness_create_device: the caller's traces lie in device memory as strided views of 1 / 2 / 4-byte elements. Refusals on
+// the host first, then the context's stream waits for the caller's, one ingest launch per circuit (ingest.hip) writes the
+// column-major Montgomery matrix bb_upload_rows would have left, and one host wait brings back the offender words. On return -
+// also on an error - nothing queued here still reads the caller's buffers. Claims come from host memory.
+std::unique_ptr<BWitness> witness_create_device(BSystem& sys, const ms_dev_matrix* traces, size_t n_claims, const u64* claim_offsets,
+                                                const u32* claim_data, void* producer_stream) {
+  Ctx& ctx = *sys.ctx;
+  HIP_CHECK(hipSetDevice(ctx.device));
+  if (!traces) throw std::runtime_error("msbb_witness_create_device: null trace list");
+  if (n_claims && (!claim_offsets || (claim_offsets[n_claims] > claim_offsets[0] && !claim_data)))
+    throw std::runtime_error("msbb_witness_create_device: null claims");
+  std::unique_ptr<BWitness> w(new BWitness());
+  w->sys = &sys;
+  const size_t C = sys.circuits.size();
+  std::vector<msamd::IngestView> views(C);
+  for (size_t ci = 0; ci < C; ci++) {
+    const BCircuit& c = sys.circuits[ci];
+    const size_t h = (size_t)traces[ci].height;
+    w->heights.push_back(h);
+    w->traces.emplace_back();
+    if (h == 0) continue;
+    if (h & (h - 1)) throw std::runtime_error("trace height must be a power of two");
+    if (log2_strict(h) + log2_strict(c.quotient_degree()) + sys.params.log_blowup > BB_TWO_ADICITY)  // baby_bear_config.rs:87
+      throw std::runtime_error("trace too tall for the two-adicity of BabyBear");
+    if (c.pre_width && h != c.pre_height) throw std::runtime_error("main trace height must equal preprocessed trace height");
+    views[ci] = msamd::ingest_check(ctx, traces[ci], ci, c.main_width, 4);
+  }
+  msamd::ingest_wait_for_producer(ctx, producer_stream);
+  try {
+    DBuf<u64> bad(ctx, C);
+    if (C) HIP_CHECK(hipMemsetAsync(bad.p, 0xFF, C * 8, ctx.stream));
+    for (size_t ci = 0; ci < C; ci++) {
+      if (!w->heights[ci]) continue;
+      w->traces[ci] = bmat(ctx, w->heights[ci], views[ci].w);
+      msamd::ingest_babybear(ctx, views[ci], w->traces[ci].buf.p, bad.p + ci);
     }
+    std::vector<u64> bad_h(C, ~u64(0));
+    ctx.d2h(bad_h.data(), bad.p, C * 8);  // the one host wait of the traces' path
+    for (size_t ci = 0; ci < C; ci++)
+      if (w->heights[ci] && bad_h[ci] != ~u64(0)) throw std::runtime_error(msamd::ingest_offender_text(ci, bad_h[ci], views[ci].w));
+  } catch (...) {
+    (void)hipStreamSynchronize(ctx.stream);  // what has been queued may still be reading the caller's buffers
+    msamd::abandon_pending();  // the read-back queued into this frame (bad_h) must not be delivered by a later synchronisation
+    throw;
   }
-  if (n_claims) {
-    std::vector<u64> offs(n_claims + 1);
-    for (size_t i = 0; i <= n_claims; i++) offs[i] = claim_offsets[i] - claim_offsets[0];
-    w->d_claim_offs = DBuf<u64>(ctx, n_claims + 1);
-    w->d_claim_data = DBuf<u32>(ctx, std::max<size_t>(flat.size(), 1));
-    ctx.h2d(w->d_claim_offs.p, offs.data(), offs.size() * 8);
-    if (!flat.empty()) ctx.h2d(w->d_claim_data.p, flat.data(), flat.size() * 4);
-    ctx.sync();
-  }
+  upload_claims(ctx, *w, n_claims, claim_offsets, claim_data);
   return w;
 }
 
@@ -2332,6 +2387,19 @@ int32_t msbb_witness_create_host(msbb_system* sys, const uint32_t* const* traces
   bool all = false;
   w->w = witness_create_host(*sys->sys, traces, heights, n_claims, claim_offsets, claim_data, &all);
   if (pinned) *pinned = all ? 1 : 0;
+  w->owner = sys;
+  sys->refs++;
+  *out = w.release();
+  return MS_OK;
+  BB_CATCH
+}
+int32_t msbb_witness_create_device(msbb_system* sys, const ms_dev_matrix* traces, size_t n_claims, const uint64_t* claim_offsets,
+                                   const uint32_t* claim_data, void* producer_stream, msbb_witness** out) {
+  if (out) *out = nullptr;
+  BB_TRY
+  if (!sys || !traces || !out) throw std::runtime_error("null argument");
+  std::unique_ptr<msbb_witness> w(new msbb_witness());
+  w->w = witness_create_device(*sys->sys, traces, n_claims, claim_offsets, claim_data, producer_stream);
   w->owner = sys;
   sys->refs++;
   *out = w.release();

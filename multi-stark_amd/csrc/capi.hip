@@ -302,6 +302,18 @@ int32_t ms_witness_prefetch(ms_witness* w, int32_t on) {
   return MS_OK;
   MS_CATCH
 }
+int32_t ms_witness_create_device(ms_system* sys, const ms_dev_matrix* traces, size_t n_claims, const uint64_t* claim_offsets,
+                                 const uint64_t* claim_data, int32_t claims_on_device, void* producer_stream, ms_witness** out) {
+  if (out) *out = nullptr;
+  MS_TRY if (!sys || !out) throw std::runtime_error("ms_witness_create_device: null argument");
+  std::unique_ptr<ms_witness> w(new ms_witness());
+  w->w = witness_create_device(*sys->sys, traces, n_claims, claim_offsets, claim_data, claims_on_device != 0, producer_stream);
+  w->owner = sys;
+  sys->refs++;
+  *out = w.release();
+  return MS_OK;
+  MS_CATCH
+}
 int32_t ms_witness_u32_add_bench(ms_system* sys, size_t num_adds, uint32_t a0, uint32_t b0, ms_witness** out) {
   *out = nullptr;
   MS_TRY std::unique_ptr<ms_witness> w(new ms_witness());

@@ -166,6 +166,10 @@ struct ReadyLookups {
 std::unique_ptr<HWitness> witness_from_device(HSystem& sys, std::vector<DBuf<u64>>&& traces, const std::vector<size_t>& heights,
                                               DBuf<u64>&& d_claim_offsets, DBuf<u64>&& d_claim_data, size_t n_claims, size_t claim_elems,
                                               std::vector<ReadyLookups>* ready = nullptr);
+// ms_witness_create_device: the caller's traces (strided views of 1 / 2 / 4 / 8-byte elements) and, optionally, its claims lie in
+// device memory; they are checked and copied by the ingest kernels (ingest.hip) and handed to witness_from_device
+std::unique_ptr<HWitness> witness_create_device(HSystem& sys, const ms_dev_matrix* traces, size_t n_claims, const u64* claim_offsets,
+                                                const u64* claim_data, bool claims_on_device, void* producer_stream);
 std::unique_ptr<HWitness> witness_u32_add_bench(HSystem& sys, size_t num_adds, u32 a0, u32 b0);
 // Blake3CompressionClaims::witness for the nine-circuit BLAKE3 system (witness_gen.hip); states_out nullable
 std::unique_ptr<HWitness> witness_blake3_compressions(HSystem& sys, size_t n, const u32* states_in, u32* states_out);

@@ -19,6 +19,7 @@
 #include <thread>
 
 #include "host.h"
+#include "ingest.h"
 #include "lookup_params.h"
 #include "open_plan.h"
 #include "quotient_params.h"
@@ -462,6 +463,97 @@ std::unique_ptr<HWitness> witness_from_device(HSystem& sys, std::vector<DBuf<u64
   w->d_claim_offsets = std::move(d_claim_offsets);
   w->d_claim_data = std::move(d_claim_data);
   return w;
+}
+
+namespace {
+// the rules of ms_witness_create for a claims list: offsets start at 0 and do not decrease, data canonical
+void check_claims(size_t n_claims, const u64* offsets, const u64* data) {
+  if (offsets[0] != 0) throw std::runtime_error("claim offsets must start at 0");
+  for (size_t i = 0; i < n_claims; i++)
+    if (offsets[i + 1] < offsets[i]) throw std::runtime_error("claim offsets must be non-decreasing");
+  for (size_t i = 0, tot = (size_t)offsets[n_claims]; i < tot; i++)
+    if (data[i] >= GL_P) throw std::runtime_error("non-canonical claim value");
+}
+}  // namespace
+
+// A witness whose traces (and, optionally, claims) the CALLER holds in device memory (ms_witness_create_device). Everything
+// that can be refused is refused on the host before the first launch; then the context's stream waits for the caller's stream,
+// one ingest launch per circuit copies and checks its trace, and ONE host wait brings back the offender words (with the
+// claims' length when the claims are on the device). witness_from_device does the rest. On return - also on an error -
+// nothing queued here still reads the caller's buffers.
+std::unique_ptr<HWitness> witness_create_device(HSystem& sys, const ms_dev_matrix* traces, size_t n_claims, const u64* claim_offsets,
+                                                const u64* claim_data, bool claims_on_device, void* producer_stream) {
+  Ctx& ctx = *sys.ctx;
+  HIP_CHECK(hipSetDevice(ctx.device));
+  const size_t C = sys.circuits.size();
+  if (!traces) throw std::runtime_error("ms_witness_create_device: null trace list");
+  if (!claim_offsets) throw std::runtime_error("ms_witness_create_device: null claim offsets");
+  std::vector<IngestView> views(C);
+  std::vector<size_t> heights(C, 0);
+  for (size_t ci = 0; ci < C; ci++) {
+    const HCircuit& c = sys.circuits[ci];
+    const size_t h = (size_t)traces[ci].height;
+    heights[ci] = h;
+    if (h == 0) continue;
+    if (h & (h - 1)) throw std::runtime_error("trace height must be a power of two");
+    if (log2_strict(h) > NTT_MAX_LOG || log2_strict(h) + sys.params.log_blowup > TW_LOG)
+      throw std::runtime_error("trace height exceeds the supported maximum");
+    if (c.pre_width && h != c.pre_height) throw std::runtime_error("main trace height must equal preprocessed trace height");
+    views[ci] = ingest_check(ctx, traces[ci], ci, c.main_width, 8);
+  }
+  size_t tot = 0;
+  if (claims_on_device) {
+    ingest_check_device_range(ctx, claim_offsets, (n_claims + 1) * 8, 8, "device claim offsets");
+  } else {
+    tot = (size_t)claim_offsets[n_claims];
+    if (tot && !claim_data) throw std::runtime_error("ms_witness_create_device: null claim data");
+    check_claims(n_claims, claim_offsets, claim_data);
+  }
+  ingest_wait_for_producer(ctx, producer_stream);
+  try {
+    DBuf<u64> bad(ctx, C);
+    if (C) HIP_CHECK(hipMemsetAsync(bad.p, 0xFF, C * 8, ctx.stream));
+    std::vector<DBuf<u64>> dtr(C);
+    for (size_t ci = 0; ci < C; ci++) {
+      if (!heights[ci]) continue;
+      dtr[ci] = DBuf<u64>(ctx, heights[ci] * views[ci].w);
+      ingest_goldilocks(ctx, views[ci], dtr[ci].p, bad.p + ci);
+    }
+    DBuf<u64> d_offs(ctx, n_claims + 1), d_data;
+    u64 tot_dev = 0;
+    if (claims_on_device) {
+      HIP_CHECK(hipMemcpyAsync(d_offs.p, claim_offsets, (n_claims + 1) * 8, hipMemcpyDeviceToDevice, ctx.stream));
+      ctx.d2h_queue(&tot_dev, claim_offsets + n_claims, 8);
+    } else {
+      d_data = DBuf<u64>(ctx, std::max<size_t>(tot, 1));
+      ctx.h2d(d_offs.p, claim_offsets, (n_claims + 1) * 8);
+      if (tot) ctx.h2d(d_data.p, claim_data, tot * 8);
+    }
+    std::vector<u64> bad_h(C, ~u64(0));
+    ctx.d2h(bad_h.data(), bad.p, C * 8);  // the one host wait of the traces' path
+    for (size_t ci = 0; ci < C; ci++)
+      if (heights[ci] && bad_h[ci] != ~u64(0)) throw std::runtime_error(ingest_offender_text(ci, bad_h[ci], views[ci].w));
+    if (claims_on_device) {
+      if (tot_dev >> 60) throw std::runtime_error("device claims: the last offset is out of range");
+      tot = (size_t)tot_dev;
+      if (tot) {
+        if (!claim_data) throw std::runtime_error("ms_witness_create_device: null claim data");
+        ingest_check_device_range(ctx, claim_data, tot * 8, 8, "device claim data");
+      }
+      d_data = DBuf<u64>(ctx, std::max<size_t>(tot, 1));
+      if (tot) HIP_CHECK(hipMemcpyAsync(d_data.p, claim_data, tot * 8, hipMemcpyDeviceToDevice, ctx.stream));
+    }
+    // Device claims are validated only below, on the host copy witness_from_device makes. That is sound because
+    // witness_from_device COPIES the two arrays (n_claims + 1 and tot words, both bounded above) and never indexes anything by
+    // an offset; should it ever start to use the offsets on the device, this check has to move in front of it.
+    std::unique_ptr<HWitness> w = witness_from_device(sys, std::move(dtr), heights, std::move(d_offs), std::move(d_data), n_claims, tot);
+    if (claims_on_device) check_claims(n_claims, w->claim_offsets.data(), w->claim_data.data());  // (from_device has brought them to the host)
+    return w;
+  } catch (...) {
+    (void)hipStreamSynchronize(ctx.stream);  // what has been queued may still be reading the caller's buffers
+    abandon_pending();  // read-backs queued into this frame (tot_dev, bad_h) must not be delivered by a later synchronisation
+    throw;
+  }
 }
 
 std::unique_ptr<HWitness> witness_create(HSystem& sys, const u64* const* traces, const u64* heights, const u64* const* mult,
