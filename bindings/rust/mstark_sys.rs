@@ -35,6 +35,10 @@ pub const MS_VERDICT_INVALID_SHAPE: i32 = 3;
 pub const MS_VERDICT_INVALID_SYSTEM: i32 = 4;
 pub const MS_VERDICT_OOD_MISMATCH: i32 = 5;
 pub const MS_VERDICT_UNBALANCED: i32 = 6;
+/// ms_witness_check: verdict mask and words per circuit of the report
+pub const MS_CHECK_CONSTRAINT: u32 = 0x1;
+pub const MS_CHECK_LOOKUPS: u32 = 0x2;
+pub const MS_CHECK_CIRCUIT_WORDS: usize = 10;
 
 /// One stage-1 trace in device memory (ms_witness_create_device / msbb_witness_create_device): element (r, c) is the unsigned
 /// little-endian integer of `elem_bytes` bytes at `ptr + (r * row_stride + c * col_stride) * elem_bytes`.
@@ -178,6 +182,9 @@ extern "C" {
     pub fn ms_system_preprocessed_mmcs(sys: *mut ms_system, out: *mut *mut ms_mmcs) -> i32;
     pub fn ms_witness_commit_stage1(w: *mut ms_witness, cap_out: *mut u8, out: *mut *mut ms_mmcs) -> i32;
     pub fn ms_challenger_observe_claims(ch: *mut ms_challenger, w: *mut ms_witness) -> i32;
+    pub fn ms_witness_check(w: *mut ms_witness, beta: *const u64, gamma: *const u64, verdict: *mut u32, circuits: *mut u64,
+                            root_counts: *mut u64, root_first: *mut u64, roots_cap: usize) -> i32;
+    pub fn ms_system_check_info(sys: *const ms_system, circuit: usize, out4: *mut u64) -> i32;
     pub fn ms_witness_claims_accumulator(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_out: *mut u64) -> i32;
     pub fn ms_stage2_build(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_in: *const u64, accs_out: *mut u64,
                            traces_out: *mut *mut ms_trace) -> i32;

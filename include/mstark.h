@@ -203,6 +203,48 @@ int32_t ms_blake3_compressions(const uint8_t* data, size_t len, uint32_t* states
 int32_t ms_witness_trace(ms_witness* w, size_t circuit, uint64_t* out, size_t cap_words, size_t* n_words);
 void ms_witness_destroy(ms_witness* w);
 
+/* ---- Witness check (what Plonky3 users know as check_constraints), on the device: does this witness satisfy the system, and
+ * if not, WHERE not - for the price of one pass over the traces and one stage-2 build instead of a proof (no LDE, no tree, no
+ * FRI). Goldilocks / BLAKE3 configuration only; a BabyBear counterpart (msbb_witness_check) does not exist yet.
+ *   Definition. For every active circuit (height n > 0) and every row r in [0, n) the circuit's user constraint roots (the
+ * `zeros` of its compiled node program, in that order, index k) are evaluated on exactly the values the quotient kernels see on
+ * the trace domain at x = w^r, w = the generator of the subgroup of order n: main and preprocessed variables at row r and, for
+ * offset 1, at row (r + 1) mod n; the selector POLYNOMIALS at x = w^r with their limits - is_first = n at row 0 (else 0),
+ * is_last = n w at row n - 1 (else 0), is_transition = w^r - w^-1 (not 0 / 1 flags); stage-2 columns and publics (read by roots
+ * that came from extension constraints) as the prover would build them under the caller's (beta, gamma): running sums that
+ * start at zero, publics [beta, gamma, acc_in, acc_out] with the accumulator chained as ms_stage2_build chains it - the claims'
+ * accumulator first, then each active circuit's total. A row fails when some root is non-zero there. The logUp constraints hold
+ * by construction of stage 2 and are not evaluated; what is checked of the lookups is the verifier's balance: the accumulator
+ * behind the last active circuit must be zero. That check is probabilistic in (beta, gamma) in the same sense as the proof is,
+ * and a row whose fingerprint makes beta + fingerprint = 0 makes it meaningless (the inverse does not exist): pick other
+ * challenges then. Not checked: anything a proof would add beyond this (the constraint degree bound, the claims' shape).
+ *   Report. *verdict: a mask of MS_CHECK_CONSTRAINT (some root is non-zero somewhere) and MS_CHECK_LOOKUPS (the accumulator
+ * does not return to zero); 0 = the witness satisfies the system. A failed check is MS_OK with a non-zero verdict; MS_ERR is for
+ * misuse. circuits: MS_CHECK_CIRCUIT_WORDS words for every circuit of the system, inactive ones included:
+ *   [0] height  [1] failing rows  [2] smallest failing row  [3] smallest failing root index at that row  [4] its value
+ *   [5] [6] the accumulator behind the circuit (zeros for an inactive circuit)  [7] number of roots  [8] diagnostics: which
+ *   kernel form ran (low byte: 1 thread per row / slots in LDS, 2 wave per row, 3 few lanes with large LDS, 4 global scratch,
+ *   0 none) and its lanes per workgroup << 8  [9] where this circuit's roots start in root_counts / root_first.
+ * [2], [3] are all-ones when no row fails. root_counts / root_first (each nullable, roots_cap entries): per root, circuit after
+ * circuit in system order, the number of rows where it is non-zero and the first such row (all-ones when none); MS_ERR_BUFFER
+ * when roots_cap is below the system's total (the sum of out4[0] of ms_system_check_info over the circuits). Every figure is deterministic.
+ *   Limits and misuse (MS_ERR, text via ms_last_error(), the context stays usable): a host-resident witness
+ * (ms_witness_create_host*: its traces are not in HBM between proofs); a witness with circuits held by another rank; beta or
+ * gamma with a coordinate >= p. Accepted: every device-resident witness - ms_witness_create, ms_witness_create_device,
+ * ms_witness_u32_add_bench, ms_witness_blake3_compressions. The witness is not changed: ms_prove behind a check writes the bytes
+ * it writes without one.
+ *   Host waits: one, for the report (plus those of the claims' upload paths it shares with ms_stage2_build). */
+#define MS_CHECK_CONSTRAINT 0x1u
+#define MS_CHECK_LOOKUPS 0x2u
+#define MS_CHECK_CIRCUIT_WORDS 10
+int32_t ms_witness_check(ms_witness* w, const uint64_t beta[2], const uint64_t gamma[2], uint32_t* verdict,
+                         uint64_t* circuits /* n_circuits x MS_CHECK_CIRCUIT_WORDS */, uint64_t* root_counts /* nullable */,
+                         uint64_t* root_first /* nullable */, size_t roots_cap);
+/* What the check adds to the nine words of ms_system_circuit_info: out4 = [number of user constraint roots =
+ * constraint_count - 2 max(num_lookups, 1), live slots of the circuit's node program, steps of its wave-per-row schedule
+ * (0: none), lanes per workgroup of the check's thread-per-row form with slots in LDS (0: the slot file does not fit)] */
+int32_t ms_system_check_info(const ms_system* sys, size_t circuit, uint64_t out4[4]);
+
 /* ---- System::prove_multiple_claims (src/prover.rs:290-603). Writes Proof::to_bytes (src/prover.rs:241-248).
  * stage_ms (optional, 6 doubles): stage1_commit, lookup_construction, stage2_commit, quotient, fri_open, total —
  * the reference's span names (src/prover.rs:336-538). Returns MS_ERR_BUFFER with *proof_len = needed size if

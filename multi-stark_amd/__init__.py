@@ -52,7 +52,7 @@ def exported_symbols():
             "ms_challenger_sample_bits", "ms_stage2_trace", "ms_claims_accumulator",
             "ms_quotient_values", "ms_field_op", "ms_trace_destroy", "ms_trace_info", "ms_system_preprocessed_mmcs",
             "ms_witness_commit_stage1", "ms_challenger_observe_claims", "ms_witness_claims_accumulator", "ms_stage2_build",
-            "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes"]
+            "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes", "ms_witness_check", "ms_system_check_info"]
 
 
 # ms_system_circuit_kernels / msbb_system_circuit_kernels (MS_KERNEL_* in include/mstark.h)
@@ -515,8 +515,93 @@ class Proof:
         return Proof(bytes(data))
 
 
+# SystemWitness.check: the challenges used when the caller gives none - fixed, non-trivial (the first hexadecimal digits of
+# pi), so that a report is reproducible. They are public: a witness made to balance under exactly these passes the lookup
+# part of the check; a caller who fears that passes its own.
+CHECK_BETA = (0x243F6A8885A308D3, 0x13198A2E03707344)
+CHECK_GAMMA = (0xA4093822299F31D0, 0x082EFA98EC4E6C89)
+CHECK_CONSTRAINT, CHECK_LOOKUPS = 0x1, 0x2  # MS_CHECK_* of include/mstark.h
+_NONE = (1 << 64) - 1
+
+
+class CircuitCheck:
+    """One circuit's part of a CheckReport (the ten words of ms_witness_check, named)."""
+
+    def __init__(self, index, words, root_counts, root_first, name=None, origins=None):
+        self.index, self.name, self.origins = index, name, origins
+        self.height, self.failing_rows = int(words[0]), int(words[1])
+        # (row, constraint root index, value) of the smallest failing row and the smallest failing root there; None = clean
+        self.first_failure = None if int(words[2]) == _NONE else (int(words[2]), int(words[3]), int(words[4]))
+        self.accumulator = (int(words[5]), int(words[6]))
+        self.roots = int(words[7])
+        self.kernel, self.lanes = int(words[8]) & 0xFF, int(words[8]) >> 8
+        self.root_counts = root_counts  # np.uint64 per root: rows where it is non-zero
+        self.root_first = root_first    # np.uint64 per root: the first such row (all-ones: none)
+
+    def fields(self):
+        """everything that is defined by the witness alone (what a model of the check reproduces)"""
+        return (self.height, self.failing_rows, self.first_failure, self.accumulator, self.roots,
+                [int(x) for x in self.root_counts], [int(x) for x in self.root_first])
+
+    def _what(self, k):
+        if self.origins is None or k >= len(self.origins) or not self.origins[k]:
+            return "constraint root %d" % k
+        o = self.origins[k]
+        names = ["constraint %d" % x[1] if x[0] == "constraint" else "ext constraint %d coordinate %d" % (x[1], x[2]) for x in o]
+        return "%s (root %d)" % (" = ".join(names), k)
+
+    def lines(self):
+        tag = "circuit %d%s" % (self.index, " (%s)" % self.name if self.name else "")
+        out = []
+        for k in np.nonzero(self.root_counts)[0]:
+            k = int(k)
+            s = "%s: %s non-zero on %d rows, first at row %d" % (tag, self._what(k), int(self.root_counts[k]), int(self.root_first[k]))
+            if self.first_failure and self.first_failure[:2] == (int(self.root_first[k]), k):
+                s += " (value 0x%016x)" % self.first_failure[2]
+            out.append(s)
+        return out
+
+
+class CheckReport:
+    """What SystemWitness.check returns: .verdict (mask of CHECK_CONSTRAINT / CHECK_LOOKUPS), .ok, .circuits[i]"""
+
+    def __init__(self, verdict, circuits, beta, gamma):
+        self.verdict, self.circuits, self.beta, self.gamma = verdict, circuits, beta, gamma
+        self.ok = verdict == 0
+        self.final_accumulator = next((c.accumulator for c in reversed(circuits) if c.height), (0, 0))
+
+    def __str__(self):
+        if self.ok:
+            return "witness satisfies the system (%d active circuits)" % sum(1 for c in self.circuits if c.height)
+        out = [ln for c in self.circuits for ln in c.lines()]
+        if self.verdict & CHECK_LOOKUPS:
+            out.append("lookups unbalanced: the accumulator ends at (0x%016x, 0x%016x)" % self.final_accumulator)
+        return "\n".join(out)
+
+
 class SystemWitness:
     """Device-resident SystemWitness + claims (ms_witness). Built by `System.witness`."""
+
+    def check(self, beta=None, gamma=None, names=None, origins=None):
+        """ms_witness_check: every user constraint root of every active circuit on the trace domain, and the lookup balance
+        under (beta, gamma) - default CHECK_BETA / CHECK_GAMMA. -> CheckReport. names / origins (optional, per circuit): labels
+        and CompiledCircuit.zero_origins for the text of the report."""
+        beta = CHECK_BETA if beta is None else tuple(int(x) for x in beta)
+        gamma = CHECK_GAMMA if gamma is None else tuple(int(x) for x in gamma)
+        sysm = self.system
+        nc = sysm.n_circuits
+        roots = [sysm.check_info(i)["roots"] for i in range(nc)]
+        total = sum(roots)
+        words = np.zeros((max(nc, 1), 10), dtype=np.uint64)
+        cnt, first = np.zeros(max(total, 1), dtype=np.uint64), np.zeros(max(total, 1), dtype=np.uint64)
+        verdict = C.c_uint32()
+        _check(lib().ms_witness_check(self.h, _p(_u64(beta)), _p(_u64(gamma)), C.byref(verdict), _p(words), _p(cnt), _p(first), C.c_size_t(total)))
+        circuits = []
+        for i in range(nc):
+            o = int(words[i, 9])
+            circuits.append(CircuitCheck(i, words[i], cnt[o:o + roots[i]].copy(), first[o:o + roots[i]].copy(),
+                                         names[i] if names else None, origins[i] if origins else None))
+        return CheckReport(int(verdict.value), circuits, beta, gamma)
 
     def __init__(self, handle, rows, system):
         self.h = handle
@@ -604,6 +689,12 @@ class System:
         keys = ["main_width", "pre_width", "pre_height", "num_lookups", "stage2_width", "constraint_count",
                 "max_constraint_degree", "quotient_degree", "args_width"]
         return dict(zip(keys, (int(x) for x in o)))
+
+    def check_info(self, ci):
+        """ms_system_check_info: what the witness check adds to circuit_info"""
+        o = np.zeros(4, dtype=np.uint64)
+        _check(lib().ms_system_check_info(self.h, C.c_size_t(ci), _p(o)))
+        return dict(zip(["roots", "slots", "wave_steps", "lds_lanes"], (int(x) for x in o)))
 
     def circuit_kernels(self, ci):
         """ms_system_circuit_kernels: the mask of KERNEL_* bits of the kernels generated and compiled for circuit `ci` (0 = the

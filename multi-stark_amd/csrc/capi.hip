@@ -357,6 +357,34 @@ int32_t ms_witness_trace(ms_witness* w, size_t circuit, uint64_t* out, size_t ca
   return MS_OK;
   MS_CATCH
 }
+int32_t ms_witness_check(ms_witness* w, const uint64_t beta[2], const uint64_t gamma[2], uint32_t* verdict, uint64_t* circuits,
+                         uint64_t* root_counts, uint64_t* root_first, size_t roots_cap) {
+  MS_TRY if (!w || !verdict || !circuits) throw std::runtime_error("ms_witness_check: null argument");
+  HWitness& wit = *w->w;
+  HSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  const E2 b = canonical_e2(beta, "beta"), g = canonical_e2(gamma, "gamma");
+  if (root_counts || root_first) {
+    size_t total = 0;
+    for (auto& c : sys.circuits) total += check_roots(c);
+    if (roots_cap < total) return MS_ERR_BUFFER;
+  }
+  witness_check(sys, wit, b, g, verdict, circuits, root_counts, root_first);
+  return MS_OK;
+  MS_CATCH
+}
+int32_t ms_system_check_info(const ms_system* sys, size_t ci, uint64_t out4[4]) {
+  MS_TRY if (!sys || !out4) throw std::runtime_error("ms_system_check_info: null argument");
+  const HSystem& s = *sys->sys;
+  if (ci >= s.circuits.size()) throw std::runtime_error("circuit index out of range");
+  const HCircuit& c = s.circuits[ci];
+  out4[0] = check_roots(c);
+  out4[1] = c.prog.n_slots;
+  out4[2] = c.prog.wave_steps;
+  out4[3] = check_lds_lanes(c.prog.n_slots);
+  return MS_OK;
+  MS_CATCH
+}
 void ms_witness_destroy(ms_witness* w) {
   if (!w) return;
   ms_system* s = w->owner;

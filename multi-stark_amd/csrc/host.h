@@ -211,6 +211,11 @@ void stage2_circuit_async(Ctx& ctx, const HSystem& sys, const HWitness& wit, siz
                           E2* total_dev);
 // the claims part of the transcript (src/prover.rs:369-373) for a device-resident witness: long lists are hashed on the device
 void observe_claims(Ctx& ctx, Challenger& ch, HWitness& wit);
+// ms_witness_check (check.hip): the user constraint roots of every active circuit on the trace domain + the lookup balance under
+// (beta, gamma). circuits: C x MS_CHECK_CIRCUIT_WORDS; root_counts / root_first (nullable): one entry per root, circuit after circuit
+void witness_check(HSystem& sys, HWitness& wit, E2 beta, E2 gamma, uint32_t* verdict, u64* circuits, u64* root_counts, u64* root_first);
+size_t check_roots(const HCircuit& c);          // constraint_count - 2 max(num_lookups, 1), checked against HCircuit::zeros
+unsigned check_lds_lanes(size_t n_slots);       // lanes per workgroup of the check's LDS tier (0: the slot file does not fit)
 void field_op(Ctx& ctx, int op, const u64* a, const u64* b, size_t n, u64* out);
 
 }  // namespace msamd

@@ -48,6 +48,7 @@ enum KernelId : int {
   K_FRI_FOLD,
   K_TRANSPOSE,
   K_OTHER,
+  K_WITNESS_CHECK,    // constraint roots on the trace domain (check.hip, ms_witness_check)
   K_COUNT
 };
 const char* kernel_name(int id);

@@ -362,6 +362,9 @@ class CompiledCircuit:
         self.main_width = main_width
         self.preprocessed = preprocessed  # None or np.ndarray (h, w) uint64
         self.lookup_prefix_len = 0
+        # per entry of `zeros`: the authored constraints it came from, ("constraint", i) or ("ext", i, coordinate); several
+        # may share a root (`zeros` is a sorted set), one folded to the constant zero appears nowhere
+        self.zero_origins = [[] for _ in zeros]
 
 
 class CircuitInputs:
@@ -394,24 +397,27 @@ def compile_circuit(inputs, d=None, w=None):
         lookups.append((m, args))
     prefix = len(it.nodes)
     zeros = []
+    authored = {}  # root -> the authored constraints that compiled to it (several may share one)
 
-    def record(root, what):
+    def record(root, what, origin):
         c = it.as_const(root)
         if c is None:
             zeros.append(root)
+            authored.setdefault(root, []).append(origin)
         elif c != 0:
             raise CompileError("UnsatisfiableConstant %s" % what)
 
     for i, c in enumerate(inputs.constraints):
-        record(it.compile_expr(c, spec, False), "constraint %d" % i)
+        record(it.compile_expr(c, spec, False), "constraint %d" % i, ("constraint", i))
     for i, c in enumerate(inputs.ext_constraints):
         if c.is_purely_base():
             raise CompileError("PurelyBaseExtConstraint %d" % i)
         for k, root in enumerate(it.expand_ext(c, spec, d, w, d == 2)):
-            record(root, "ext constraint %d coord %d" % (i, k))
+            record(root, "ext constraint %d coord %d" % (i, k), ("ext", i, k))
     zeros = sorted(set(zeros))
     cc = CompiledCircuit(it.nodes, zeros, lookups, inputs.main_width, pre)
     cc.lookup_prefix_len = prefix
+    cc.zero_origins = [authored[z] for z in zeros]
     return cc
 
 
