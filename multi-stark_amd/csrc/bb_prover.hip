@@ -9,165 +9,18 @@
 #include <mutex>
 
 #include "../../include/mstark_bb.h"
-#include "bb.h"
-#include "bb_verify_dev.h"
+#include "bb_host.h"
 #include "ingest.h"
 
 namespace msbb {
 
-using msamd::PNode;
-
-static unsigned log2_strict(size_t n) {
-  unsigned l = 0;
-  while ((size_t(1) << l) < n) l++;
-  return l;
-}
-static size_t bitrev_host(size_t x, unsigned bits) {
-  size_t r = 0;
-  for (unsigned i = 0; i < bits; i++) r |= ((x >> i) & 1) << (bits - 1 - i);
-  return r;
-}
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// DuplexChallenger<BabyBear, Poseidon2BabyBear<16>, 16, 8> (baby_bear_config.rs:37), values in Montgomery form
-struct Challenger {
-  const Poseidon2* perm;
-  u32 state[16];
-  std::vector<u32> input, output;
-  explicit Challenger(const Poseidon2* p) : perm(p) {
-    for (auto& x : state) x = 0;
-  }
-  void duplexing() {
-    for (size_t i = 0; i < input.size(); i++) state[i] = input[i];
-    input.clear();
-    bb_poseidon2(*perm, state);
-    output.assign(state, state + 8);
-  }
-  void observe(u32 m) {
-    output.clear();
-    input.push_back(m);
-    if (input.size() == 8) duplexing();
-  }
-  void observe_usize(u64 x) { observe(bb_to_monty((u32)(x % BB_P))); }  // Val::from_usize
-  void observe_e4(E4 e) {
-    for (int k = 0; k < 4; k++) observe(e.c[k]);
-  }
-  void observe_cap(const std::vector<Digest8>& cap) {
-    for (auto& d : cap)
-      for (int k = 0; k < 8; k++) observe(d.w[k]);
-  }
-  u32 sample() {
-    if (!input.empty() || output.empty()) duplexing();
-    u32 v = output.back();
-    output.pop_back();
-    return v;
-  }
-  E4 sample_e4() {
-    E4 e;
-    for (int k = 0; k < 4; k++) e.c[k] = sample();
-    return e;
-  }
-  size_t sample_bits(unsigned bits) { return (size_t)(bb_from_monty(sample()) & ((1u << bits) - 1)); }
-  // smallest witness (canonical value); ZERO at 0 bits - the deterministic rule of src/types.rs:72-81
-  u32 grind(unsigned bits) {
-    if (bits == 0) return 0;
-    for (u32 w = 0; w < BB_P; w++) {
-      Challenger c = *this;
-      c.observe(bb_to_monty(w));
-      if (c.sample_bits(bits) == 0) {
-        observe(bb_to_monty(w));
-        sample_bits(bits);
-        return w;
-      }
-    }
-    throw std::runtime_error("grind: no witness");
-  }
-};
-
-struct Params {
-  u64 log_blowup = 1, cap_height = 0, log_final_poly_len = 0, max_log_arity = 1, num_queries = 1, commit_pow_bits = 0, query_pow_bits = 0;
-};
-struct BCircuit {
-  std::vector<PNode> nodes;
-  std::vector<uint32_t> degrees, zeros;
-  std::vector<std::pair<uint32_t, std::vector<uint32_t>>> lookups;
-  size_t main_width = 0, pre_width = 0, pre_height = 0, num_lookups = 0, stage2_width = 0, constraint_count = 0, max_constraint_degree = 0,
-         args_width = 0, lookup_prefix_len = 0;
-  BProgram prog;
-  msamd::JitKernel quotient_jit;  // this circuit's quotient kernel, compiled at system creation (quotient_jit.hip); may be empty
-  BLookupsDev lk;
-  DBuf<u32> d_zeros;
-  BMat pre;  // preprocessed trace (column-major, Montgomery), for witness preparation
-  size_t quotient_degree() const {
-    size_t d = (max_constraint_degree > 2 ? max_constraint_degree : 2) - 1, q = 1;
-    while (q < d) q <<= 1;
-    return q;
-  }
-};
-struct BSystem {
-  Ctx* ctx = nullptr;
-  Params params;
-  Poseidon2 perm;
-  DBuf<Poseidon2> d_perm;
-  std::vector<BCircuit> circuits;
-  bool has_pre = false;
-  std::vector<Digest8> pre_commit;
-  std::vector<int> pre_indices;
-  BPcsData pre_data;
-  std::vector<u32> seed;  // Montgomery form
-};
-struct BWitness {
-  BSystem* sys = nullptr;
-  std::vector<size_t> heights;
-  std::vector<BMat> traces;
-  std::vector<std::vector<u32>> claims;  // canonical (the transcript absorbs them on the host)
-  DBuf<u32> d_claim_data;                // Montgomery form, concatenated
-  DBuf<u64> d_claim_offs;
-  // host-resident form (msbb_witness_create_host): nothing lives in HBM between proofs; every prove() uploads the caller's
-  // (page-locked) trace buffers and the claims, and gives the device copies back when it is done
-  bool host_resident = false;
-  bool pinned = true;  // every trace buffer could be page-locked (otherwise the uploads go through the context's bounce buffer)
-  std::vector<const u32*> h_traces;
-  std::vector<void*> registered;
-  std::vector<u32> h_claims_monty;
-  std::vector<u64> h_claim_offs;
-  ~BWitness() {
-    if (!registered.empty() && sys && sys->ctx) {  // nothing may still be reading the caller's ranges when they lose their page lock
-      (void)hipSetDevice(sys->ctx->device);
-      (void)hipStreamSynchronize(sys->ctx->main_stream);
-    }
-    for (void* p : registered) msamd::host_range_unpin(p);
-  }
-};
 
 static std::vector<Digest8> tree_cap(Ctx& ctx, const BTree& t) {
   size_t l = t.cap_layer();
   std::vector<Digest8> cap(t.sizes[l]);
   ctx.d2h(cap.data(), t.layers[l].p, cap.size() * sizeof(Digest8));
   return cap;
-}
-
-namespace {
-struct Reader {
-  const uint8_t* p;
-  size_t n, off = 0;
-  u64 word() {
-    if (off + 8 > n) throw std::runtime_error("system blob truncated");
-    u64 v = 0;
-    for (int k = 0; k < 8; k++) v |= (u64)p[off + k] << (8 * k);
-    off += 8;
-    return v;
-  }
-};
-}  // namespace
-static const u64 BLOB_MAGIC = 0x31304259534D0000ULL;  // "\0\0MSYB01"
-
-static void set_internal_diag(Poseidon2& k) {
-  auto m = [](u32 canonical) { return bb_to_monty(canonical); };
-  u32 half = bb_inv(m(2)), i8 = bb_inv(m(256)), i27 = bb_inv(m(1u << 27));
-  u32 t[16] = {bb_neg(m(2)), m(1), m(2), half, m(3), m(4), bb_neg(half), bb_neg(m(3)), bb_neg(m(4)), i8, bb_inv(m(4)), bb_inv(m(8)), i27,
-               bb_neg(i8), bb_neg(bb_inv(m(16))), bb_neg(i27)};
-  for (int i = 0; i < 16; i++) k.diag[i] = t[i];
 }
 
 std::unique_ptr<BSystem> system_from_blob(Ctx& ctx, const uint8_t* blob, size_t len) {
@@ -523,7 +376,6 @@ struct W {
     for (auto& d : c) dig(d);
   }
 };
-typedef std::vector<std::vector<std::vector<E4>>> OpenedRound;  // matrix -> point -> column
 void write_round(W& w, const OpenedRound& r) {
   w.u64_(r.size());
   for (auto& m : r) {
@@ -647,7 +499,7 @@ void pcs_open(BSystem& sys, const std::vector<OpenRound>& rounds, Challenger& ch
         E4 scale = e4_mul_base(vanish, bb_inv(bb_mul(s_pow, bb_to_monty((u32)(h % BB_P)))));
         for (auto& y : sums) {
           y = e4_mul(y, scale);
-          ch.observe_e4(y);
+          ch.observe_ext(y);
         }
         per_point.push_back(std::move(sums));
       }
@@ -656,7 +508,7 @@ void pcs_open(BSystem& sys, const std::vector<OpenRound>& rounds, Challenger& ch
     opened.push_back(std::move(orr));
   }
 
-  E4 alpha = ch.sample_e4();
+  E4 alpha = ch.sample_ext();
   std::vector<E4> apow(gw + 1);
   apow[0] = e4_one();
   for (size_t i = 1; i <= gw; i++) apow[i] = e4_mul(apow[i - 1], alpha);
@@ -796,7 +648,7 @@ void pcs_open(BSystem& sys, const std::vector<OpenRound>& rounds, Challenger& ch
       ch.observe_cap(cap);
       fri.commits.push_back(cap);
       fri.pow_witnesses.push_back(grind(sys, ch, (unsigned)prm.commit_pow_bits));
-      E4 beta = ch.sample_e4();
+      E4 beta = ch.sample_ext();
       // a round of arity 2^la is la binary folds with beta, beta^2, beta^4, ...; the vector rolled in behind it takes
       // beta^(2^la), the square of the last step's challenge (bb_fri_fold's own roll-in factor)
       const E4* src = cur;
@@ -834,7 +686,7 @@ void pcs_open(BSystem& sys, const std::vector<OpenRound>& rounds, Challenger& ch
       ch.observe_cap(caps[i]);
       fri.commits.push_back(caps[i]);
       fri.pow_witnesses.push_back(0);
-      if (!e4_eq(ch.sample_e4(), hb[i].beta)) throw std::runtime_error("FRI: device transcript diverged from the host challenger");
+      if (!e4_eq(ch.sample_ext(), hb[i].beta)) throw std::runtime_error("FRI: device transcript diverged from the host challenger");
     }
   }
   if (next_in != inputs.size()) throw std::runtime_error("FRI: an input was never rolled in");
@@ -854,7 +706,7 @@ void pcs_open(BSystem& sys, const std::vector<OpenRound>& rounds, Challenger& ch
         tw = bb_mul(tw, step);
       }
       fri.final_poly[k] = e4_mul_base(acc, n_inv);
-      ch.observe_e4(fri.final_poly[k]);
+      ch.observe_ext(fri.final_poly[k]);
     }
   }
   fri.query_pow_witness = grind(sys, ch, (unsigned)prm.query_pow_bits);
@@ -1008,10 +860,10 @@ std::vector<uint8_t> prove(BSystem& sys, BWitness& wit, double* stage_ms) {
     ch.observe_usize(c.size());
     for (u32 x : c) ch.observe(bb_to_monty(x));
   }
-  E4 beta = ch.sample_e4();
-  ch.observe_e4(beta);
-  E4 gamma = ch.sample_e4();
-  ch.observe_e4(gamma);
+  E4 beta = ch.sample_ext();
+  ch.observe_ext(beta);
+  E4 gamma = ch.sample_ext();
+  ch.observe_ext(gamma);
   // claims accumulator, src/prover.rs:382-387
   E4 acc = bb_claims_accumulator(ctx, wit.d_claim_data.p, wit.d_claim_offs.p, wit.claims.size(), beta, gamma);
 
@@ -1042,8 +894,8 @@ std::vector<uint8_t> prove(BSystem& sys, BWitness& wit, double* stage_ms) {
   std::vector<Digest8> s2_cap = tree_cap(ctx, s2.tree);
   if (stage_ms) stage_ms[2] = now_ms() - t0;
   ch.observe_cap(s2_cap);
-  for (auto& a : accumulators) ch.observe_e4(a);
-  E4 alpha = ch.sample_e4();
+  for (auto& a : accumulators) ch.observe_ext(a);
+  E4 alpha = ch.sample_ext();
 
   // ---- quotient
   t0 = now_ms();
@@ -1077,7 +929,7 @@ std::vector<uint8_t> prove(BSystem& sys, BWitness& wit, double* stage_ms) {
 
   // ---- opening
   t0 = now_ms();
-  E4 zeta = ch.sample_e4();
+  E4 zeta = ch.sample_ext();
   std::vector<OpenRound> rounds(3);
   rounds[0].data = &s1, rounds[1].data = &s2, rounds[2].data = &qd;
   for (unsigned ld : log_degrees) {
@@ -1126,1129 +978,6 @@ std::vector<uint8_t> prove(BSystem& sys, BWitness& wit, double* stage_ms) {
   return std::move(w.b);
 }
 
-
-// ------------------------------------------------------------------ verify
-// System::verify_multiple_claims (/root/reference/src/verifier.rs:208-532, shape checks :536-695) for this
-// configuration, over the bytes msbb_prove writes. All host code (a verification is a few thousand permutations);
-// written against the reference's verifier, independently of the oracle's. Codes: the VerificationError variants
-// (src/verifier.rs:176-192) as in include/mstark.h.
-namespace {
-enum : int { V_OK = 0, V_INVALID_OPENING = 2, V_INVALID_SHAPE = 3, V_INVALID_SYSTEM = 4, V_OOD_MISMATCH = 5, V_UNBALANCED = 6 };
-struct Malformed {};
-struct PReader {
-  const uint8_t* p;
-  size_t n, pos = 0;
-  void need(size_t k) const {
-    if (k > n - pos) throw Malformed();
-  }
-  uint8_t u8() {
-    need(1);
-    return p[pos++];
-  }
-  u64 u64_() {
-    need(8);
-    u64 v;
-    memcpy(&v, p + pos, 8);
-    pos += 8;
-    return v;
-  }
-  size_t count(size_t elem_bytes) {
-    u64 c = u64_();
-    if (elem_bytes && c > (n - pos) / elem_bytes) throw Malformed();
-    return (size_t)c;
-  }
-  u32 field() {  // the Montgomery word of a MontyField31; serde rejects words >= p
-    need(4);
-    u32 v;
-    memcpy(&v, p + pos, 4);
-    pos += 4;
-    if (v >= BB_P) throw Malformed();
-    return v;
-  }
-  E4 ext() {
-    E4 e;
-    for (int k = 0; k < 4; k++) e.c[k] = field();
-    return e;
-  }
-  Digest8 digest() {
-    Digest8 d;
-    for (int k = 0; k < 8; k++) d.w[k] = field();
-    return d;
-  }
-  std::vector<Digest8> cap() {
-    std::vector<Digest8> v(count(32));
-    for (auto& d : v) d = digest();
-    return v;
-  }
-};
-OpenedRound read_round(PReader& r) {
-  OpenedRound out(r.count(8));
-  for (auto& m : out) {
-    m.resize(r.count(8));
-    for (auto& pt : m) {
-      pt.resize(r.count(16));
-      for (auto& e : pt) e = r.ext();
-    }
-  }
-  return out;
-}
-struct VBatchOpening {
-  std::vector<std::vector<u32>> rows;
-  std::vector<Digest8> path;
-};
-struct VFriStep {
-  unsigned log_arity = 1;
-  std::vector<E4> siblings;  // the opened row without the queried position's own value
-  std::vector<Digest8> path;
-};
-struct VQuery {
-  std::vector<VBatchOpening> inputs;
-  std::vector<VFriStep> steps;
-};
-struct VProof {
-  std::vector<uint8_t> active, log_degrees;
-  std::vector<Digest8> s1, s2, q;
-  std::vector<E4> accs;
-  std::vector<std::vector<Digest8>> commits;
-  std::vector<u32> pow;
-  std::vector<VQuery> queries;
-  std::vector<E4> final_poly;
-  u32 query_pow = 0;
-  OpenedRound q_opened, pre_opened, s1_opened, s2_opened;
-  bool has_pre = false;
-};
-VProof parse_proof(const uint8_t* bytes, size_t len) {
-  PReader r{bytes, len};
-  VProof p;
-  p.active.resize(r.count(1));
-  for (auto& a : p.active) {
-    a = r.u8();
-    if (a > 1) throw Malformed();
-  }
-  p.s1 = r.cap(), p.s2 = r.cap(), p.q = r.cap();
-  p.accs.resize(r.count(16));
-  for (auto& a : p.accs) a = r.ext();
-  p.log_degrees.resize(r.count(1));
-  for (auto& l : p.log_degrees) l = r.u8();
-  p.commits.resize(r.count(8));
-  for (auto& c : p.commits) c = r.cap();
-  p.pow.resize(r.count(4));
-  for (auto& w : p.pow) w = r.field();
-  p.queries.resize(r.count(8));
-  for (auto& q : p.queries) {
-    q.inputs.resize(r.count(8));
-    for (auto& bo : q.inputs) {
-      bo.rows.resize(r.count(8));
-      for (auto& row : bo.rows) {
-        row.resize(r.count(4));
-        for (auto& v : row) v = r.field();
-      }
-      bo.path.resize(r.count(32));
-      for (auto& d : bo.path) d = r.digest();
-    }
-    q.steps.resize(r.count(8));
-    for (auto& st : q.steps) {
-      st.log_arity = r.u8();
-      if (st.log_arity < 1 || st.log_arity > BB_FRI_MAX_LOG_ARITY) throw Malformed();
-      st.siblings.resize(r.count(16));
-      if (st.siblings.size() != (size_t(1) << st.log_arity) - 1) throw Malformed();
-      for (auto& e : st.siblings) e = r.ext();
-      st.path.resize(r.count(32));
-      for (auto& d : st.path) d = r.digest();
-    }
-  }
-  p.final_poly.resize(r.count(16));
-  for (auto& e : p.final_poly) e = r.ext();
-  p.query_pow = r.field();
-  p.q_opened = read_round(r);
-  {
-    const uint8_t tag = r.u8();
-    if (tag > 1) throw Malformed();
-    p.has_pre = tag != 0;
-  }
-  if (p.has_pre) p.pre_opened = read_round(r);
-  p.s1_opened = read_round(r);
-  p.s2_opened = read_round(r);
-  if (r.pos != len) throw Malformed();
-  return p;
-}
-bool e4_is_zero(E4 a) { return !(a.c[0] | a.c[1] | a.c[2] | a.c[3]); }
-
-// PaddingFreeSponge / TruncatedPermutation on the host
-Digest8 hash_words(const Poseidon2& perm, const std::vector<u32>& v) {
-  u32 st[16] = {0};
-  for (size_t i = 0; i < v.size(); i += 8) {
-    size_t k = std::min<size_t>(8, v.size() - i);
-    for (size_t j = 0; j < k; j++) st[j] = v[i + j];
-    bb_poseidon2(perm, st);
-  }
-  Digest8 d;
-  for (int j = 0; j < 8; j++) d.w[j] = st[j];
-  return d;
-}
-Digest8 compress_host(const Poseidon2& perm, const Digest8& l, const Digest8& r) {
-  u32 st[16];
-  for (int j = 0; j < 8; j++) st[j] = l.w[j], st[8 + j] = r.w[j];
-  bb_poseidon2(perm, st);
-  Digest8 d;
-  for (int j = 0; j < 8; j++) d.w[j] = st[j];
-  return d;
-}
-struct Dim {
-  size_t w, h;
-};
-bool mmcs_verify_batch(const Poseidon2& perm, const std::vector<Digest8>& cap, const std::vector<Dim>& dims, size_t index, const VBatchOpening& o) {
-  if (dims.size() != o.rows.size() || dims.empty()) return false;
-  std::vector<size_t> order(dims.size());
-  for (size_t i = 0; i < dims.size(); i++) {
-    order[i] = i;
-    if (o.rows[i].size() != dims[i].w) return false;
-    if (dims[i].h == 0 || (dims[i].h & (dims[i].h - 1))) return false;
-  }
-  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return dims[a].h > dims[b].h; });
-  size_t pos = 0, cur = dims[order[0]].h;
-  const unsigned log_max = log2_strict(cur);
-  auto hash_group = [&](size_t height) {
-    std::vector<u32> buf;
-    while (pos < order.size() && dims[order[pos]].h == height) {
-      auto& v = o.rows[order[pos]];
-      buf.insert(buf.end(), v.begin(), v.end());
-      pos++;
-    }
-    return hash_words(perm, buf);
-  };
-  Digest8 root = hash_group(cur);
-  const size_t capn = cap.size();
-  if (capn == 0 || (capn & (capn - 1))) return false;
-  const unsigned chh = log2_strict(capn);
-  if (chh > log_max || o.path.size() != log_max - chh) return false;
-  size_t idx = index;
-  if (idx >= (size_t(1) << log_max)) return false;
-  for (auto& sib : o.path) {
-    root = (idx & 1) ? compress_host(perm, sib, root) : compress_host(perm, root, sib);
-    idx >>= 1;
-    cur >>= 1;
-    if (pos < order.size() && dims[order[pos]].h == cur) root = compress_host(perm, root, hash_group(cur));
-  }
-  if (pos != order.size()) return false;
-  return memcmp(root.w, cap[idx].w, 32) == 0;
-}
-bool check_witness(Challenger& ch, unsigned bits, u32 monty_witness) {
-  if (bits == 0) return true;
-  ch.observe(monty_witness);
-  return ch.sample_bits(bits) == 0;
-}
-struct RoundClaim {
-  std::vector<Digest8> commit;
-  std::vector<unsigned> log_n;
-  std::vector<std::vector<std::pair<E4, const std::vector<E4>*>>> mats;
-};
-// TwoAdicFriPcs::verify + verify_fri / verify_query (p3-fri 0.5.1)
-bool pcs_verify(const BSystem& sys, const std::vector<RoundClaim>& rounds, const VProof& proof, Challenger& ch) {
-  const Params& prm = sys.params;
-  const Poseidon2& perm = sys.perm;
-  const unsigned lb = (unsigned)prm.log_blowup;
-  for (auto& r : rounds)
-    for (auto& m : r.mats)
-      for (auto& pv : m)
-        for (auto& y : *pv.second) ch.observe_e4(y);
-  const E4 alpha = ch.sample_e4();
-  const size_t nrounds = proof.commits.size();
-  if (proof.pow.size() != nrounds) return false;
-  // every query repeats the rounds' arities; the first one's place the tallest input, each is checked against the schedule below
-  std::vector<unsigned> arities(nrounds, 1);
-  if (!proof.queries.empty()) {
-    if (proof.queries[0].steps.size() != nrounds) return false;
-    for (size_t i = 0; i < nrounds; i++) arities[i] = proof.queries[0].steps[i].log_arity;
-  }
-  unsigned log_gmax = (unsigned)(lb + prm.log_final_poly_len);
-  for (unsigned a : arities) {
-    if (a > prm.max_log_arity) return false;
-    log_gmax += a;
-  }
-  if (log_gmax > BB_TWO_ADICITY) return false;
-  std::vector<E4> betas;
-  for (size_t i = 0; i < nrounds; i++) {
-    ch.observe_cap(proof.commits[i]);
-    if (!check_witness(ch, (unsigned)prm.commit_pow_bits, proof.pow[i])) return false;
-    betas.push_back(ch.sample_e4());
-  }
-  if (proof.final_poly.size() != (size_t(1) << prm.log_final_poly_len)) return false;
-  for (auto& c : proof.final_poly) ch.observe_e4(c);
-  if (proof.queries.size() != prm.num_queries) return false;
-  if (!check_witness(ch, (unsigned)prm.query_pow_bits, proof.query_pow)) return false;
-  const unsigned log_final_height = (unsigned)(lb + prm.log_final_poly_len);
-  const u32 g = bb_to_monty(BB_GENERATOR);
-  for (auto& qp : proof.queries) {
-    const size_t index = ch.sample_bits(log_gmax);
-    if (qp.inputs.size() != rounds.size()) return false;
-    std::map<unsigned, std::pair<E4, E4>> ro;  // log height -> (running alpha power, reduced opening)
-    for (size_t ri = 0; ri < rounds.size(); ri++) {
-      const RoundClaim& r = rounds[ri];
-      const VBatchOpening& bo = qp.inputs[ri];
-      if (bo.rows.size() != r.mats.size()) return false;
-      std::vector<Dim> dims;
-      unsigned log_bmax = 0;
-      for (size_t mi = 0; mi < r.mats.size(); mi++) {
-        dims.push_back(Dim{bo.rows[mi].size(), size_t(1) << (r.log_n[mi] + lb)});
-        log_bmax = std::max(log_bmax, r.log_n[mi] + lb);
-      }
-      if (log_bmax > log_gmax) return false;
-      if (!mmcs_verify_batch(perm, r.commit, dims, index >> (log_gmax - log_bmax), bo)) return false;
-      for (size_t mi = 0; mi < r.mats.size(); mi++) {
-        const unsigned lh = r.log_n[mi] + lb;
-        const size_t rev = bitrev_host(index >> (log_gmax - lh), lh);
-        const u32 x = bb_mul(g, bb_pow(bb_two_adic_generator(lh), rev));
-        auto it = ro.find(lh);
-        if (it == ro.end()) it = ro.emplace(lh, std::make_pair(e4_one(), e4_zero())).first;
-        for (auto& pv : r.mats[mi]) {
-          if (pv.second->size() != bo.rows[mi].size()) return false;
-          E4 den = pv.first;
-          den.c[0] = bb_sub(den.c[0], x);
-          if (e4_is_zero(den)) return false;
-          const E4 quot = e4_inv(den);
-          for (size_t c = 0; c < pv.second->size(); c++) {
-            E4 diff = (*pv.second)[c];
-            diff.c[0] = bb_sub(diff.c[0], bo.rows[mi][c]);
-            it->second.second = e4_add(it->second.second, e4_mul(e4_mul(it->second.first, diff), quot));
-            it->second.first = e4_mul(it->second.first, alpha);
-          }
-        }
-      }
-    }
-    auto low = ro.find(lb);  // a height-1 trace gives a constant polynomial: its reduced opening must vanish
-    if (low != ro.end() && log_final_height >= lb && lb < log_gmax) {
-      if (!e4_is_zero(low->second.second)) return false;
-      ro.erase(low);
-    }
-    if (qp.steps.size() != nrounds) return false;
-    auto it = ro.rbegin();
-    if (it == ro.rend() || it->first != log_gmax) return false;
-    E4 folded = it->second.second;
-    ++it;
-    size_t idx = index;
-    unsigned log_height = log_gmax;
-    for (size_t i = 0; i < nrounds; i++) {
-      const VFriStep& st = qp.steps[i];
-      const unsigned la = st.log_arity;
-      if (la != arities[i] || log_height <= log_final_height) return false;
-      {  // the schedule: as far as max_log_arity allows without stepping over the next input or below the final height
-        unsigned want = std::min<unsigned>((unsigned)prm.max_log_arity, log_height - log_final_height);
-        if (it != ro.rend()) want = std::min(want, log_height - it->first);
-        if (la != want) return false;
-      }
-      const unsigned log_folded_height = log_height - la;
-      const size_t m = size_t(1) << la, own = idx & (m - 1), row = idx >> la;
-      std::vector<E4> evals(m);
-      for (size_t j = 0, k = 0; j < m; j++) evals[j] = j == own ? folded : st.siblings[k++];
-      VBatchOpening bo;
-      bo.rows.emplace_back();
-      for (auto& e : evals)
-        for (int k = 0; k < 4; k++) bo.rows[0].push_back(e.c[k]);  // ExtensionMmcs: flattened row
-      bo.path = st.path;
-      if (!mmcs_verify_batch(perm, proof.commits[i], {Dim{4 * m, size_t(1) << log_folded_height}}, row, bo)) return false;
-      idx = row;
-      if (la == 1) {
-        // fold_row: the line through (x0, e0), (-x0, e1) evaluated at beta; x0 = w^bitrev(idx) on the subgroup
-        const u32 x0 = bb_pow(bb_two_adic_generator(log_folded_height + 1), bitrev_host(idx, log_folded_height));
-        const u32 x1 = bb_neg(x0);
-        const E4 slope = e4_mul_base(e4_sub(evals[1], evals[0]), bb_inv(bb_sub(x1, x0)));
-        E4 bx = betas[i];
-        bx.c[0] = bb_sub(bx.c[0], x0);
-        folded = e4_add(evals[0], e4_mul(bx, slope));
-      } else {
-        // position j of the row holds the value at h_j = x w^bitrev(j), w of order m = 2^la, x = w_{2^log_height}^bitrev(row); fold_row
-        // is the polynomial of degree < m through them at beta, in barycentric form over the coset x <w>:
-        // p(beta) = (beta^m - x^m) / (m x^m) * sum_j e_j h_j / (beta - h_j)
-        const u32 x = bb_pow(bb_two_adic_generator(log_height), bitrev_host(row, log_folded_height));
-        const u32 wm = bb_two_adic_generator(la);
-        E4 sum = e4_zero();
-        bool hit = false;
-        for (size_t j = 0; j < m && !hit; j++) {
-          const u32 h = bb_mul(x, bb_pow(wm, bitrev_host(j, la)));
-          E4 d = betas[i];
-          d.c[0] = bb_sub(d.c[0], h);
-          if (e4_is_zero(d)) {  // beta is one of the row's points
-            folded = evals[j];
-            hit = true;
-          } else {
-            sum = e4_add(sum, e4_mul(e4_mul_base(evals[j], h), e4_inv(d)));
-          }
-        }
-        if (!hit) {
-          const u32 xm = bb_pow(x, m);
-          E4 z = betas[i];
-          for (unsigned k = 0; k < la; k++) z = e4_square(z);
-          z.c[0] = bb_sub(z.c[0], xm);
-          folded = e4_mul(e4_mul_base(z, bb_inv(bb_mul(xm, bb_to_monty((u32)m)))), sum);
-        }
-      }
-      log_height = log_folded_height;
-      if (it != ro.rend() && it->first == log_folded_height) {
-        // roll-in factor: the next power of beta after the 2^la the fold used (beta^2 for a binary round)
-        E4 f = betas[i];
-        for (unsigned k = 0; k < la; k++) f = e4_square(f);
-        folded = e4_add(folded, e4_mul(f, it->second.second));
-        ++it;
-      }
-    }
-    if (it != ro.rend()) return false;
-    const u32 x = bb_pow(bb_two_adic_generator(log_gmax), bitrev_host(idx, log_gmax));
-    E4 eval = e4_zero();
-    for (size_t k = proof.final_poly.size(); k-- > 0;) eval = e4_add(e4_mul_base(eval, x), proof.final_poly[k]);
-    if (!e4_eq(eval, folded)) return false;
-  }
-  return true;
-}
-// src/lookup.rs:103-118 over extension-valued coordinates
-void coord_mul_e(const E4* a, const E4* b, E4* out) {
-  E4 lo[4], hi[4];
-  for (int k = 0; k < 4; k++) lo[k] = hi[k] = e4_zero();
-  for (int i = 0; i < 4; i++)
-    for (int j = 0; j < 4; j++) {
-      E4 p = e4_mul(a[i], b[j]);
-      if (i + j < 4)
-        lo[i + j] = e4_add(lo[i + j], p);
-      else
-        hi[i + j - 4] = e4_add(hi[i + j - 4], p);
-    }
-  const u32 w = bb_to_monty(BB_EXT_W);
-  for (int k = 0; k < 4; k++) out[k] = e4_add(lo[k], e4_mul_base(hi[k], w));
-}
-
-// What verify() knows of one proof once the transcript has been replayed up to zeta: the parsed proof, the challenges, the
-// PCS rounds to check (they point into `proof`) and the challenger in the state Pcs::verify starts from.
-struct Prepared {
-  VProof proof;
-  std::vector<size_t> aidx, qdeg;
-  E4 beta, gamma, acc, alpha, zeta;
-  std::vector<RoundClaim> rounds;
-  Challenger ch;
-  explicit Prepared(const Poseidon2* perm) : ch(perm) {}
-};
-
-// parse, verify_shape and the transcript replay: V_OK, or the verdict that ends the verification here
-int verify_prepare(const BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* claim_data, const uint8_t* proof_bytes,
-                   size_t proof_len, Prepared& P) {
-  const Params& prm = sys.params;
-  const size_t C = sys.circuits.size();
-  if (C == 0) return V_INVALID_SYSTEM;
-  VProof& proof = P.proof;
-  try {
-    proof = parse_proof(proof_bytes, proof_len);
-  } catch (const Malformed&) {
-    return V_INVALID_SHAPE;
-  }
-  // ---- verify_shape (src/verifier.rs:536-695)
-  if (proof.active.size() != C) return V_INVALID_SHAPE;
-  std::vector<size_t>& aidx = P.aidx;
-  std::vector<int> apos(C, -1);
-  for (size_t i = 0; i < C; i++)
-    if (proof.active[i]) {
-      apos[i] = (int)aidx.size();
-      aidx.push_back(i);
-    }
-  const size_t na = aidx.size();
-  if (na == 0 || proof.log_degrees.size() != na) return V_INVALID_SHAPE;
-  size_t num_pre = 0;
-  for (int pi : sys.pre_indices) num_pre += pi >= 0;
-  if (sys.has_pre != (num_pre != 0)) return V_INVALID_SYSTEM;
-  if ((proof.has_pre ? proof.pre_opened.size() : 0) != num_pre) return V_INVALID_SHAPE;
-  for (size_t ci = 0; ci < C; ci++)
-    if (sys.pre_indices[ci] >= 0 && !proof.active[ci] && proof.pre_opened[sys.pre_indices[ci]].size() != 0) return V_INVALID_SHAPE;
-  if (proof.s1_opened.size() != na || proof.s2_opened.size() != na || proof.q_opened.size() != na) return V_INVALID_SHAPE;
-  std::vector<size_t>& qdeg = P.qdeg;
-  for (size_t pos = 0; pos < na; pos++) {
-    const size_t ci = aidx[pos];
-    const BCircuit& c = sys.circuits[ci];
-    const int slot = sys.pre_indices[ci];
-    if (proof.s1_opened[pos].size() != 2 || proof.s2_opened[pos].size() != 2) return V_INVALID_SHAPE;
-    if (slot >= 0 && proof.pre_opened[slot].size() != 2) return V_INVALID_SHAPE;
-    for (int j = 0; j < 2; j++) {
-      if (slot >= 0 && proof.pre_opened[slot][j].size() != c.pre_width) return V_INVALID_SHAPE;
-      if (proof.s1_opened[pos][j].size() != c.main_width) return V_INVALID_SHAPE;
-      if (proof.s2_opened[pos][j].size() != c.stage2_width) return V_INVALID_SHAPE;
-    }
-    const size_t qd = c.quotient_degree();
-    if (proof.log_degrees[pos] + log2_strict(qd) > BB_TWO_ADICITY - prm.log_blowup) return V_INVALID_SHAPE;  // baby_bear_config.rs:87
-    if (c.pre_width && (size_t(1) << proof.log_degrees[pos]) != c.pre_height) return V_INVALID_SHAPE;
-    qdeg.push_back(qd);
-    if (proof.q_opened[pos].size() != 1 || proof.q_opened[pos][0].size() != qd * 4) return V_INVALID_SHAPE;
-  }
-  if (proof.accs.size() != na) return V_INVALID_SHAPE;
-  if (!e4_is_zero(proof.accs.back())) return V_UNBALANCED;  // src/verifier.rs:242-246
-
-  // ---- transcript replay (src/verifier.rs:255-326)
-  for (size_t i = 0; i < n_claims; i++)
-    if (claim_offsets[i + 1] < claim_offsets[i]) return V_INVALID_SHAPE;
-  const size_t claim_elems = n_claims ? (size_t)claim_offsets[n_claims] : 0;
-  for (size_t i = 0; i < claim_elems; i++)
-    if (claim_data[i] >= BB_P) return V_INVALID_SHAPE;
-  Challenger& ch = P.ch;
-  for (u32 v : sys.seed) ch.observe(v);
-  ch.observe_usize(C);
-  for (auto& c : sys.circuits) {
-    ch.observe_usize(c.constraint_count), ch.observe_usize(c.max_constraint_degree), ch.observe_usize(c.pre_height);
-    ch.observe_usize(c.pre_width), ch.observe_usize(c.main_width), ch.observe_usize(c.stage2_width);
-  }
-  for (auto a : proof.active) ch.observe(a ? BB_R1 : 0);
-  if (sys.has_pre) ch.observe_cap(sys.pre_commit);
-  ch.observe_cap(proof.s1);
-  for (auto ld : proof.log_degrees) ch.observe_usize(ld);
-  ch.observe_usize(n_claims);
-  for (size_t i = 0; i < n_claims; i++) {
-    ch.observe_usize(claim_offsets[i + 1] - claim_offsets[i]);
-    for (u64 k = claim_offsets[i]; k < claim_offsets[i + 1]; k++) ch.observe(bb_to_monty(claim_data[k]));
-  }
-  const E4 beta = P.beta = ch.sample_e4();
-  ch.observe_e4(beta);
-  const E4 gamma = P.gamma = ch.sample_e4();
-  ch.observe_e4(gamma);
-  ch.observe_cap(proof.s2);
-  for (auto& a : proof.accs) ch.observe_e4(a);
-  E4& acc = P.acc;
-  acc = e4_zero();
-  for (size_t i = 0; i < n_claims; i++) {
-    E4 f = e4_zero();
-    for (u64 k = claim_offsets[i + 1]; k-- > claim_offsets[i];) {
-      f = e4_mul(f, gamma);
-      f.c[0] = bb_add(f.c[0], bb_to_monty(claim_data[k]));
-    }
-    const E4 m = e4_add(beta, f);
-    if (e4_is_zero(m)) return V_INVALID_SHAPE;  // the reference would divide by zero here
-    acc = e4_add(acc, e4_inv(m));
-  }
-  P.alpha = ch.sample_e4();
-  ch.observe_cap(proof.q);
-  const E4 zeta = P.zeta = ch.sample_e4();
-
-  std::vector<RoundClaim>& rounds = P.rounds;
-  rounds.assign(3, RoundClaim());
-  rounds[0].commit = proof.s1, rounds[1].commit = proof.s2, rounds[2].commit = proof.q;
-  for (size_t pos = 0; pos < na; pos++) {
-    const unsigned ld = proof.log_degrees[pos];
-    const E4 zn = e4_mul_base(zeta, bb_two_adic_generator(ld));
-    rounds[0].log_n.push_back(ld);
-    rounds[0].mats.push_back({{zeta, &proof.s1_opened[pos][0]}, {zn, &proof.s1_opened[pos][1]}});
-    rounds[1].log_n.push_back(ld);
-    rounds[1].mats.push_back({{zeta, &proof.s2_opened[pos][0]}, {zn, &proof.s2_opened[pos][1]}});
-    rounds[2].log_n.push_back(ld);
-    rounds[2].mats.push_back({{zeta, &proof.q_opened[pos][0]}});
-  }
-  if (sys.has_pre) {
-    RoundClaim r0;
-    r0.commit = sys.pre_commit;
-    for (size_t ci = 0; ci < C; ci++) {
-      const int slot = sys.pre_indices[ci];
-      if (slot < 0) continue;
-      if (apos[ci] >= 0) {
-        const unsigned ld = proof.log_degrees[apos[ci]];
-        const E4 zn = e4_mul_base(zeta, bb_two_adic_generator(ld));
-        r0.log_n.push_back(ld);
-        r0.mats.push_back({{zeta, &proof.pre_opened[slot][0]}, {zn, &proof.pre_opened[slot][1]}});
-      } else {
-        r0.log_n.push_back(log2_strict(sys.circuits[ci].pre_height));
-        r0.mats.push_back({});
-      }
-    }
-    rounds.push_back(std::move(r0));
-  }
-  return V_OK;
-}
-
-// the out-of-domain check per circuit (src/verifier.rs:419-530), after Pcs::verify has accepted
-int verify_ood(const BSystem& sys, const Prepared& P) {
-  const VProof& proof = P.proof;
-  const std::vector<size_t>&aidx = P.aidx, &qdeg = P.qdeg;
-  const size_t na = aidx.size();
-  const E4 beta = P.beta, gamma = P.gamma, alpha = P.alpha, zeta = P.zeta;
-  E4 acc = P.acc;
-  for (size_t pos = 0; pos < na; pos++) {
-    const size_t ci = aidx[pos];
-    const BCircuit& c = sys.circuits[ci];
-    const unsigned ld = proof.log_degrees[pos];
-    const E4 next_acc = proof.accs[pos];
-    const u32 g_n = bb_two_adic_generator(ld), g_inv = bb_inv(g_n);
-    E4 zh = e4_exp_pow2(zeta, ld);  // selectors_at_point
-    zh.c[0] = bb_sub(zh.c[0], BB_R1);
-    E4 z1 = zeta, zg = zeta;
-    z1.c[0] = bb_sub(z1.c[0], BB_R1);
-    zg.c[0] = bb_sub(zg.c[0], g_inv);
-    if (e4_is_zero(zh) || e4_is_zero(z1) || e4_is_zero(zg)) return V_OOD_MISMATCH;
-    const E4 is_first = e4_mul(zh, e4_inv(z1)), is_last = e4_mul(zh, e4_inv(zg)), is_trans = zg, inv_van = e4_inv(zh);
-    const u32 inj_norm = bb_inv(bb_mul(bb_to_monty((u32)((u64(1) << ld) % BB_P)), g_n));
-    const E4 four[4] = {beta, gamma, acc, next_acc};
-    E4 publics[16];
-    for (int k = 0; k < 4; k++)
-      for (int d = 0; d < 4; d++) publics[4 * k + d] = e4_base(four[k].c[d]);
-    const int slot = sys.pre_indices[ci];
-    const std::vector<E4>* rows[3][2] = {{slot >= 0 ? &proof.pre_opened[slot][0] : nullptr, slot >= 0 ? &proof.pre_opened[slot][1] : nullptr},
-                                         {&proof.s1_opened[pos][0], &proof.s1_opened[pos][1]},
-                                         {&proof.s2_opened[pos][0], &proof.s2_opened[pos][1]}};
-    std::vector<E4> buf(c.nodes.size());
-    for (size_t i = 0; i < c.nodes.size(); i++) {  // ConstraintGraph::sweep_range over the extension field
-      const PNode& n = c.nodes[i];
-      E4 v;
-      switch (n.kind) {
-        case msamd::OP_CONST: v = e4_base(bb_to_monty((u32)n.a)); break;
-        case msamd::OP_VAR: {
-          if (n.source > 2 || n.offset > 1) return V_INVALID_SYSTEM;
-          const std::vector<E4>* row = rows[n.source][n.offset];
-          if (!row || n.a >= row->size()) return V_INVALID_SYSTEM;
-          v = (*row)[n.a];
-          break;
-        }
-        case msamd::OP_PUBLIC:
-          if (n.a >= 16) return V_INVALID_SYSTEM;
-          v = publics[n.a];
-          break;
-        case msamd::OP_IS_FIRST: v = is_first; break;
-        case msamd::OP_IS_LAST: v = is_last; break;
-        case msamd::OP_IS_TRANS: v = is_trans; break;
-        case msamd::OP_ADD: v = e4_add(buf[n.a], buf[n.b]); break;
-        case msamd::OP_SUB: v = e4_sub(buf[n.a], buf[n.b]); break;
-        case msamd::OP_MUL: v = e4_mul(buf[n.a], buf[n.b]); break;
-        default: v = e4_neg(buf[n.a]); break;
-      }
-      buf[i] = v;
-    }
-    std::vector<E4> cv;
-    for (auto z : c.zeros) cv.push_back(buf[z]);
-    // logup_constraint_values, generic-degree path (src/lookup.rs:210-256)
-    const std::vector<E4>&s2 = proof.s2_opened[pos][0], &s2n = proof.s2_opened[pos][1];
-    E4 inj[4];
-    for (int d = 0; d < 4; d++) inj[d] = e4_mul(is_last, e4_mul_base(e4_sub(publics[12 + d], publics[8 + d]), inj_norm));
-    if (c.lookups.empty()) {
-      for (int d = 0; d < 4; d++) cv.push_back(e4_add(e4_sub(s2n[d], s2[d]), inj[d]));
-    } else {
-      const size_t last = c.lookups.size() - 1;
-      for (size_t j = 0; j < c.lookups.size(); j++) {
-        const auto& l = c.lookups[j];
-        E4 diff[4], f[4], t[4];
-        for (int d = 0; d < 4; d++) {
-          const E4 tgt = j < last ? s2[4 * (j + 1) + d] : e4_add(s2n[d], inj[d]);
-          diff[d] = e4_sub(tgt, s2[4 * j + d]);
-          f[d] = e4_zero();
-        }
-        for (size_t k = l.second.size(); k-- > 0;) {
-          coord_mul_e(f, publics + 4, t);
-          for (int d = 0; d < 4; d++) f[d] = t[d];
-          f[0] = e4_add(f[0], buf[l.second[k]]);
-        }
-        for (int d = 0; d < 4; d++) f[d] = e4_add(f[d], publics[d]);
-        coord_mul_e(f, diff, t);
-        cv.push_back(e4_sub(t[0], buf[l.first]));
-        for (int d = 1; d < 4; d++) cv.push_back(t[d]);
-      }
-    }
-    if (cv.size() != c.constraint_count) return V_INVALID_SYSTEM;
-    E4 comp = e4_zero();
-    for (auto& x : cv) comp = e4_add(e4_mul(comp, alpha), x);
-    // Q(zeta) = sum_i zeta^(i n) c_i(zeta), each chunk given by its four base-field coordinate polynomials
-    const std::vector<E4>& qrow = proof.q_opened[pos][0];
-    const E4 zpn = e4_exp_pow2(zeta, ld);
-    E4 zp = e4_one(), quot = e4_zero();
-    for (size_t i = 0; i < qdeg[pos]; i++) {
-      E4 chunk = e4_zero();
-      for (int d = 0; d < 4; d++) {
-        E4 basis = e4_zero();
-        basis.c[d] = BB_R1;  // X^d
-        chunk = e4_add(chunk, e4_mul(qrow[4 * i + d], basis));
-      }
-      quot = e4_add(quot, e4_mul(zp, chunk));
-      zp = e4_mul(zp, zpn);
-    }
-    if (!e4_eq(e4_mul(comp, inv_van), quot)) return V_OOD_MISMATCH;
-    acc = next_acc;
-  }
-  return V_OK;
-}
-
-}  // namespace
-
-int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* claim_data, const uint8_t* proof_bytes, size_t proof_len) {
-  Prepared P(&sys.perm);
-  const int v = verify_prepare(sys, n_claims, claim_offsets, claim_data, proof_bytes, proof_len, P);
-  if (v != V_OK) return v;
-  if (!pcs_verify(sys, P.rounds, P.proof, P.ch)) return V_INVALID_OPENING;
-  return verify_ood(sys, P);
-}
-
-// ---------------------------------------------------------------- batched verification (msbb_verify_batch, msbb_mmcs_verify_batch)
-// The host keeps what is serial or cheap - parsing, verify_shape, the transcript replay, both proof-of-work checks, the query
-// indices, the arity schedule and the out-of-domain check - and makes EVERY structural check of pcs_verify before a value is
-// read. What remains per query (reduced openings, fold chain, final polynomial) and per Merkle path goes to the device as flat
-// arrays whose offsets all come from the lengths validated here (bb_verify_dev.h); a proof refused on the host adds nothing to them.
-namespace {
-
-struct BVBatch {
-  std::vector<u32> words, u32s, qmap;
-  std::vector<E4> ext;
-  std::vector<Digest8> digs;
-  std::vector<BVPathItem> items;
-  std::vector<BVProofDesc> proofs;
-  std::vector<BVMatDesc> mats;
-  std::vector<BVHeightDesc> heights;
-  size_t n_flags = 0, fri_words = 0, ro_count = 0;
-  double path_bytes = 0;
-  size_t bytes() const {
-    return (words.size() + u32s.size() + qmap.size() + fri_words) * 4 + (ext.size() + ro_count) * sizeof(E4) + digs.size() * sizeof(Digest8) +
-           items.size() * sizeof(BVPathItem);
-  }
-};
-const size_t BV_FLUSH_BYTES = size_t(256) << 20;  // a batch larger than this goes to the device in several parts
-
-struct PathPlan {
-  std::vector<size_t> order;  // the matrices in walk order: stable by descending height
-  std::vector<u32> groups;    // per level 0 .. path_len: 1 + words of the matrices of height max >> level, 0 = none
-  unsigned log_max = 0;
-};
-// everything mmcs_verify_batch refuses without hashing, and the walk order of what it would hash: false = refused
-bool mmcs_plan(const std::vector<Dim>& dims, size_t capn, size_t path_len, PathPlan& pl) {
-  if (dims.empty()) return false;
-  pl.order.resize(dims.size());
-  for (size_t i = 0; i < dims.size(); i++) {
-    pl.order[i] = i;
-    if (dims[i].h == 0 || (dims[i].h & (dims[i].h - 1))) return false;
-  }
-  std::stable_sort(pl.order.begin(), pl.order.end(), [&](size_t a, size_t b) { return dims[a].h > dims[b].h; });
-  pl.log_max = log2_strict(dims[pl.order[0]].h);
-  if (capn == 0 || (capn & (capn - 1))) return false;
-  const unsigned ch = log2_strict(capn);
-  if (ch > pl.log_max || path_len != pl.log_max - ch) return false;
-  std::vector<u64> gw(path_len + 1, 0);
-  std::vector<uint8_t> present(path_len + 1, 0);
-  for (size_t i : pl.order) {
-    const size_t k = pl.log_max - log2_strict(dims[i].h);
-    if (k > path_len) return false;  // shorter than the cap layer: never injected (pos != order.size())
-    gw[k] += dims[i].w;
-    present[k] = 1;
-  }
-  pl.groups.assign(path_len + 1, 0);
-  for (size_t k = 0; k <= path_len; k++) {
-    if (gw[k] >= 0xffffffffu) return false;  // (no proof or caller can hold four billion words in one row)
-    if (present[k]) pl.groups[k] = 1 + (u32)gw[k];
-  }
-  return true;
-}
-
-// the FRI leaf rows live behind the uploaded words: settle the offsets that count from them
-void bvbatch_seal(BVBatch& B) {
-  for (auto& it : B.items)
-    if (it.fri_row) {
-      it.vals_off += B.words.size();
-      it.fri_row = 0;
-    }
-  for (auto& p : B.proofs) p.fri_off += B.words.size();
-}
-
-template <class T>
-size_t bv_place(size_t& off, size_t count) {
-  off = (off + 63) & ~size_t(63);
-  const size_t at = off;
-  off += count * sizeof(T);
-  return at;
-}
-
-// upload, two launches, one read-back: fail[flag] != 0 where a device check of that flag's owner failed
-void bvbatch_run(Ctx& ctx, const Poseidon2* d_perm, BVBatch& B, std::vector<u32>& fail) {
-  fail.assign(B.n_flags, 0);
-  if (B.items.empty() && B.qmap.empty()) return;
-  bvbatch_seal(B);
-  size_t off = 0;
-  const size_t at_items = bv_place<BVPathItem>(off, B.items.size()), at_proofs = bv_place<BVProofDesc>(off, B.proofs.size());
-  const size_t at_mats = bv_place<BVMatDesc>(off, B.mats.size()), at_heights = bv_place<BVHeightDesc>(off, B.heights.size());
-  const size_t at_u32s = bv_place<u32>(off, B.u32s.size()), at_qmap = bv_place<u32>(off, B.qmap.size());
-  const size_t at_ext = bv_place<E4>(off, B.ext.size()), at_digs = bv_place<Digest8>(off, B.digs.size());
-  const size_t at_fail = bv_place<u32>(off, B.n_flags), at_words = bv_place<u32>(off, B.words.size());
-  const size_t up = off;
-  off += B.fri_words * 4;
-  const size_t at_ro = bv_place<E4>(off, B.ro_count);
-  size_t total = 4096;
-  while (total < off) total <<= 1;  // few distinct sizes: the context's pool keeps blocks by exact size
-  if (ctx.verify_stage_cap < up) {
-    HIP_CHECK(hipStreamSynchronize(ctx.stream));
-    if (ctx.verify_stage) (void)hipHostFree(ctx.verify_stage);
-    ctx.verify_stage = nullptr;
-    ctx.verify_stage_cap = 0;
-    size_t cap = size_t(1) << 20;
-    while (cap < up) cap <<= 1;
-    HIP_CHECK(hipHostMalloc((void**)&ctx.verify_stage, cap, hipHostMallocDefault));
-    ctx.verify_stage_cap = cap;
-  }
-  uint8_t* st = ctx.verify_stage;
-  auto put = [&](size_t at, const void* src, size_t n) {
-    if (n) memcpy(st + at, src, n);
-  };
-  put(at_items, B.items.data(), B.items.size() * sizeof(BVPathItem));
-  put(at_proofs, B.proofs.data(), B.proofs.size() * sizeof(BVProofDesc));
-  put(at_mats, B.mats.data(), B.mats.size() * sizeof(BVMatDesc));
-  put(at_heights, B.heights.data(), B.heights.size() * sizeof(BVHeightDesc));
-  put(at_u32s, B.u32s.data(), B.u32s.size() * 4);
-  put(at_qmap, B.qmap.data(), B.qmap.size() * 4);
-  put(at_ext, B.ext.data(), B.ext.size() * sizeof(E4));
-  put(at_digs, B.digs.data(), B.digs.size() * sizeof(Digest8));
-  memset(st + at_fail, 0, B.n_flags * 4);
-  put(at_words, B.words.data(), B.words.size() * 4);
-  DBuf<uint8_t> dev(ctx, total);
-  HIP_CHECK(hipMemcpyAsync(dev.p, st, up, hipMemcpyHostToDevice, ctx.stream));
-  BVDev d;
-  d.items = (const BVPathItem*)(dev.p + at_items);
-  d.proofs = (const BVProofDesc*)(dev.p + at_proofs);
-  d.mats = (const BVMatDesc*)(dev.p + at_mats);
-  d.heights = (const BVHeightDesc*)(dev.p + at_heights);
-  d.u32s = (const u32*)(dev.p + at_u32s);
-  d.qmap = (const u32*)(dev.p + at_qmap);
-  d.ext = (const E4*)(dev.p + at_ext);
-  d.digs = (const Digest8*)(dev.p + at_digs);
-  d.fail = (u32*)(dev.p + at_fail);
-  d.words = (u32*)(dev.p + at_words);
-  d.ro = (E4*)(dev.p + at_ro);
-  d.perm = d_perm;
-  bbv_launch(ctx, d, B.qmap.size(), B.items.size(), B.path_bytes);
-  ctx.d2h(fail.data(), d.fail, B.n_flags * 4);  // the call's one host wait (the staging buffer is free again after it)
-}
-
-void bv_add_item(BVBatch& B, const PathPlan& pl, u64 vals_off, bool fri_row, u64 index, u32 sib_off, u32 cap_off, u32 grp_off, u32 flag) {
-  BVPathItem it;
-  it.vals_off = vals_off;
-  it.index = index;
-  it.sib_off = sib_off;
-  it.cap_off = cap_off;
-  it.grp_off = grp_off;
-  it.n_levels = (u32)(pl.groups.size() - 1);
-  it.flag = flag;
-  it.fri_row = fri_row ? 1 : 0;  // resolved by bvbatch_seal
-  B.items.push_back(it);
-  double w = 0;
-  for (u32 g : pl.groups) w += g ? g - 1 : 0;
-  B.path_bytes += 4 * w + 32.0 * (it.n_levels + 1);
-}
-
-// pcs_verify with the per-query arithmetic and the Merkle paths left to the device.
-//   COLLECT_REFUSED  pcs_verify returns false here, whatever the values are (nothing was added to B)
-//   COLLECT_QUEUED   the verdict is B's flag `flag` after bvbatch_run
-//   COLLECT_HOST     queries open a matrix that is opened at no point (the preprocessed trace of an inactive circuit) with
-//                    different widths. The padding-free sponge can hash such rows to one digest, so pcs_verify may accept
-//                    them; the flat layout has one width per matrix, and the caller runs pcs_verify itself on this proof
-//                    (nothing was added to B). No prover output has this form.
-enum { COLLECT_REFUSED = 0, COLLECT_QUEUED, COLLECT_HOST };
-int pcs_collect(const BSystem& sys, const std::vector<RoundClaim>& rounds, const VProof& proof, Challenger& ch, BVBatch& B, u32 flag) {
-  const Params& prm = sys.params;
-  const unsigned lb = (unsigned)prm.log_blowup;
-  for (auto& r : rounds)
-    for (auto& m : r.mats)
-      for (auto& pv : m)
-        for (auto& y : *pv.second) ch.observe_e4(y);
-  const E4 alpha = ch.sample_e4();
-  const size_t nrounds = proof.commits.size();
-  if (proof.pow.size() != nrounds) return COLLECT_REFUSED;
-  std::vector<unsigned> arities(nrounds, 1);
-  if (!proof.queries.empty()) {
-    if (proof.queries[0].steps.size() != nrounds) return COLLECT_REFUSED;
-    for (size_t i = 0; i < nrounds; i++) arities[i] = proof.queries[0].steps[i].log_arity;
-  }
-  unsigned log_gmax = (unsigned)(lb + prm.log_final_poly_len);
-  for (unsigned a : arities) {
-    if (a > prm.max_log_arity) return COLLECT_REFUSED;
-    log_gmax += a;
-  }
-  if (log_gmax > BB_TWO_ADICITY) return COLLECT_REFUSED;
-  std::vector<E4> betas;
-  for (size_t i = 0; i < nrounds; i++) {
-    ch.observe_cap(proof.commits[i]);
-    if (!check_witness(ch, (unsigned)prm.commit_pow_bits, proof.pow[i])) return COLLECT_REFUSED;
-    betas.push_back(ch.sample_e4());
-  }
-  if (proof.final_poly.size() != (size_t(1) << prm.log_final_poly_len)) return COLLECT_REFUSED;
-  for (auto& c : proof.final_poly) ch.observe_e4(c);
-  if (proof.queries.size() != prm.num_queries) return COLLECT_REFUSED;
-  if (!check_witness(ch, (unsigned)prm.query_pow_bits, proof.query_pow)) return COLLECT_REFUSED;
-  const unsigned log_final_height = (unsigned)(lb + prm.log_final_poly_len);
-  const size_t nq = proof.queries.size(), R = rounds.size();
-  if (nq == 0) return COLLECT_QUEUED;  // nothing is queried: pcs_verify accepts here as well (the flag stays clear)
-  std::vector<size_t> index(nq);
-  for (size_t q = 0; q < nq; q++) index[q] = ch.sample_bits(log_gmax);
-
-  // ---- the input rounds' structure, from the first query
-  struct RoundPlan {
-    PathPlan pl;
-    unsigned log_bmax = 0;
-    std::vector<size_t> width, row_off;  // per matrix: words, and where its row lies in a query's block
-    size_t words = 0, path_len = 0;
-  };
-  std::vector<RoundPlan> rp(R);
-  const VQuery& q0 = proof.queries[0];
-  if (q0.inputs.size() != R) return COLLECT_REFUSED;
-  size_t blk = 1;  // word 0 of a query's block is its index
-  std::map<unsigned, std::vector<std::pair<size_t, size_t>>, std::greater<unsigned>> by_height;  // (round, matrix) in ro's order
-  for (size_t ri = 0; ri < R; ri++) {
-    const RoundClaim& r = rounds[ri];
-    const VBatchOpening& bo = q0.inputs[ri];
-    RoundPlan& P = rp[ri];
-    if (bo.rows.size() != r.mats.size()) return COLLECT_REFUSED;
-    std::vector<Dim> dims;
-    for (size_t mi = 0; mi < r.mats.size(); mi++) {
-      dims.push_back(Dim{bo.rows[mi].size(), size_t(1) << (r.log_n[mi] + lb)});
-      P.log_bmax = std::max(P.log_bmax, r.log_n[mi] + lb);
-      P.width.push_back(bo.rows[mi].size());
-      for (auto& pv : r.mats[mi])
-        if (pv.second->size() != bo.rows[mi].size()) return COLLECT_REFUSED;
-      by_height[r.log_n[mi] + lb].push_back({ri, mi});
-    }
-    if (P.log_bmax > log_gmax) return COLLECT_REFUSED;
-    P.path_len = bo.path.size();
-    if (!mmcs_plan(dims, r.commit.size(), P.path_len, P.pl)) return COLLECT_REFUSED;
-    P.row_off.resize(dims.size());
-    for (size_t i : P.pl.order) {
-      P.row_off[i] = blk + P.words;
-      P.words += dims[i].w;
-    }
-    blk += P.words;
-  }
-  // ---- heights of the reduced openings, descending, and the fold chain's schedule
-  std::vector<unsigned> hs;
-  for (auto& kv : by_height) hs.push_back(kv.first);
-  const bool zero_rule = by_height.count(lb) && log_final_height >= lb && lb < log_gmax;  // lb is the lowest height: the last slot
-  const size_t n_chain = hs.size() - (zero_rule ? 1 : 0);
-  if (n_chain == 0 || hs[0] != log_gmax) return COLLECT_REFUSED;
-  struct StepPlan {
-    PathPlan pl;
-    size_t path_len = 0, row_off = 0, sib_off = 0;
-    unsigned shift = 0;  // the round's row index is the query index >> shift
-  };
-  std::vector<StepPlan> sp(nrounds);
-  size_t fri_stride = 0, sib_stride = 0;
-  {
-    size_t hp = 1;
-    unsigned lh = log_gmax, shift = 0;
-    for (size_t i = 0; i < nrounds; i++) {
-      const unsigned la = arities[i];
-      if (lh <= log_final_height) return COLLECT_REFUSED;
-      unsigned want = std::min<unsigned>((unsigned)prm.max_log_arity, lh - log_final_height);
-      if (hp < n_chain) want = std::min(want, lh - hs[hp]);
-      if (la != want) return COLLECT_REFUSED;
-      lh -= la;
-      shift += la;
-      const size_t m = size_t(1) << la;
-      sp[i].path_len = q0.steps[i].path.size();
-      sp[i].shift = shift;
-      sp[i].row_off = fri_stride;
-      sp[i].sib_off = sib_stride;
-      if (!mmcs_plan({Dim{4 * m, size_t(1) << lh}}, proof.commits[i].size(), sp[i].path_len, sp[i].pl)) return COLLECT_REFUSED;
-      fri_stride += 4 * m;
-      sib_stride += m - 1;
-      if (hp < n_chain && hs[hp] == lh) hp++;
-    }
-    if (hp != n_chain) return COLLECT_REFUSED;
-  }
-  // ---- every query has that structure
-  for (auto& qp : proof.queries) {
-    if (qp.inputs.size() != R || qp.steps.size() != nrounds) return COLLECT_REFUSED;
-    for (size_t ri = 0; ri < R; ri++) {
-      const VBatchOpening& bo = qp.inputs[ri];
-      if (bo.rows.size() != rp[ri].width.size()) return COLLECT_REFUSED;
-      for (size_t mi = 0; mi < bo.rows.size(); mi++)
-        if (bo.rows[mi].size() != rp[ri].width[mi]) return rounds[ri].mats[mi].empty() ? COLLECT_HOST : COLLECT_REFUSED;
-      if (bo.path.size() != rp[ri].path_len) return COLLECT_REFUSED;
-    }
-    for (size_t i = 0; i < nrounds; i++) {
-      const VFriStep& st = qp.steps[i];
-      if (st.log_arity != arities[i] || st.siblings.size() != (size_t(1) << arities[i]) - 1 || st.path.size() != sp[i].path_len) return COLLECT_REFUSED;
-    }
-  }
-
-  // ---- accepted so far: append
-  BVProofDesc D;
-  memset(&D, 0, sizeof(D));
-  D.alpha = alpha;
-  D.blk_off = B.words.size();
-  D.blk_stride = blk;
-  D.fri_off = B.fri_words;  // (bvbatch_seal adds the uploaded words in front)
-  D.fri_stride = fri_stride;
-  D.ro_off = B.ro_count;
-  D.sib_stride = (u32)sib_stride;
-  D.n_rounds = (u32)nrounds;
-  D.log_gmax = log_gmax;
-  D.query0 = (u32)B.qmap.size();
-  D.flag = flag;
-  D.n_heights = (u32)hs.size();
-  D.zero_slot = zero_rule ? (u32)(hs.size() - 1) : ~u32(0);
-  D.height_off = (u32)B.heights.size();
-  for (unsigned lh : hs) {
-    auto& list = by_height[lh];
-    BVHeightDesc H;
-    H.lh = lh;
-    H.mat_off = (u32)B.mats.size();
-    H.n_mats = (u32)list.size();
-    H.pad = 0;
-    B.heights.push_back(H);
-    for (auto& rm : list) {
-      const auto& pts = rounds[rm.first].mats[rm.second];
-      BVMatDesc M;
-      M.row_off = (u32)rp[rm.first].row_off[rm.second];
-      M.width = (u32)rp[rm.first].width[rm.second];
-      M.n_points = (u32)pts.size();
-      M.pv_off = (u32)B.ext.size();
-      B.mats.push_back(M);
-      for (auto& pv : pts) {
-        B.ext.push_back(pv.first);
-        B.ext.insert(B.ext.end(), pv.second->begin(), pv.second->end());
-      }
-    }
-  }
-  D.beta_off = (u32)B.ext.size();
-  B.ext.insert(B.ext.end(), betas.begin(), betas.end());
-  D.final_off = (u32)B.ext.size();
-  D.n_final = (u32)proof.final_poly.size();
-  B.ext.insert(B.ext.end(), proof.final_poly.begin(), proof.final_poly.end());
-  D.arity_off = (u32)B.u32s.size();
-  for (unsigned a : arities) B.u32s.push_back(a);
-  std::vector<u32> grp_in(R), cap_in(R), grp_fri(nrounds), cap_fri(nrounds);
-  for (size_t ri = 0; ri < R; ri++) {
-    grp_in[ri] = (u32)B.u32s.size();
-    B.u32s.insert(B.u32s.end(), rp[ri].pl.groups.begin(), rp[ri].pl.groups.end());
-    cap_in[ri] = (u32)B.digs.size();
-    B.digs.insert(B.digs.end(), rounds[ri].commit.begin(), rounds[ri].commit.end());
-  }
-  for (size_t i = 0; i < nrounds; i++) {
-    grp_fri[i] = (u32)B.u32s.size();
-    B.u32s.insert(B.u32s.end(), sp[i].pl.groups.begin(), sp[i].pl.groups.end());
-    cap_fri[i] = (u32)B.digs.size();
-    B.digs.insert(B.digs.end(), proof.commits[i].begin(), proof.commits[i].end());
-  }
-  D.sib_off = (u32)B.ext.size();
-  const u32 proof_slot = (u32)B.proofs.size();
-  for (size_t q = 0; q < nq; q++) {
-    const VQuery& qp = proof.queries[q];
-    B.words.push_back((u32)index[q]);
-    for (size_t ri = 0; ri < R; ri++) {
-      const VBatchOpening& bo = qp.inputs[ri];
-      const u64 vals_off = B.words.size();
-      for (size_t i : rp[ri].pl.order) B.words.insert(B.words.end(), bo.rows[i].begin(), bo.rows[i].end());
-      const u32 sib = (u32)B.digs.size();
-      B.digs.insert(B.digs.end(), bo.path.begin(), bo.path.end());
-      bv_add_item(B, rp[ri].pl, vals_off, false, index[q] >> (log_gmax - rp[ri].log_bmax), sib, cap_in[ri], grp_in[ri], flag);
-    }
-    for (size_t i = 0; i < nrounds; i++) {
-      const VFriStep& st = qp.steps[i];
-      B.ext.insert(B.ext.end(), st.siblings.begin(), st.siblings.end());
-      const u32 sib = (u32)B.digs.size();
-      B.digs.insert(B.digs.end(), st.path.begin(), st.path.end());
-      bv_add_item(B, sp[i].pl, B.fri_words + q * fri_stride + sp[i].row_off, true, index[q] >> sp[i].shift, sib, cap_fri[i], grp_fri[i], flag);
-    }
-    B.qmap.push_back(proof_slot);
-  }
-  B.fri_words += nq * fri_stride;
-  B.ro_count += nq * hs.size();
-  B.proofs.push_back(D);
-  return COLLECT_QUEUED;
-}
-
-}  // namespace
-
-void verify_batch(BSystem& sys, size_t n_proofs, const u64* n_claims, const u64* const* claim_offsets, const u32* const* claim_data,
-                  const uint8_t* const* proofs, const u64* proof_lens, int32_t* verdicts) {
-  Ctx& ctx = *sys.ctx;
-  HIP_CHECK(hipSetDevice(ctx.device));
-  static const u64 no_offsets[1] = {0};
-  BVBatch B;
-  std::vector<std::pair<size_t, int>> waiting;  // (proof, its out-of-domain verdict): the device decides between that and 2
-  std::vector<u32> fail;
-  auto flush = [&]() {
-    B.n_flags = waiting.size();
-    bvbatch_run(ctx, sys.d_perm.p, B, fail);
-    for (size_t k = 0; k < waiting.size(); k++) verdicts[waiting[k].first] = fail[k] ? V_INVALID_OPENING : waiting[k].second;
-    waiting.clear();
-    B = BVBatch();
-  };
-  for (size_t i = 0; i < n_proofs; i++) {
-    const u64* offs = n_claims[i] ? claim_offsets[i] : no_offsets;
-    Prepared P(&sys.perm);
-    const int v = verify_prepare(sys, (size_t)n_claims[i], offs, claim_data ? claim_data[i] : nullptr, proofs[i], (size_t)proof_lens[i], P);
-    if (v != V_OK) {
-      verdicts[i] = v;
-      continue;
-    }
-    const Challenger at_pcs = P.ch;
-    const int c = pcs_collect(sys, P.rounds, P.proof, P.ch, B, (u32)waiting.size());
-    if (c == COLLECT_HOST) {
-      Challenger ch = at_pcs;
-      verdicts[i] = pcs_verify(sys, P.rounds, P.proof, ch) ? verify_ood(sys, P) : V_INVALID_OPENING;
-      continue;
-    }
-    if (c == COLLECT_REFUSED) {
-      verdicts[i] = V_INVALID_OPENING;
-      continue;
-    }
-    waiting.push_back({i, verify_ood(sys, P)});
-    if (B.bytes() > BV_FLUSH_BYTES) flush();
-  }
-  flush();
-}
-
-// MerkleTreeMmcs::verify_batch for many openings of one commitment, one device thread per opening; everything canonical
-void mmcs_verify_batch_device(Ctx& ctx, const Poseidon2* d_perm, const std::vector<size_t>& heights, const std::vector<size_t>& widths,
-                              const u32* cap, unsigned cap_height, size_t n_openings, const u64* indices, const u32* vals, const u32* siblings,
-                              uint8_t* ok_out) {
-  HIP_CHECK(hipSetDevice(ctx.device));
-  if (n_openings == 0) return;
-  std::vector<Dim> dims;
-  size_t max_h = 0, row_words = 0;
-  for (size_t i = 0; i < heights.size(); i++) {
-    if (heights[i] == 0 || (heights[i] & (heights[i] - 1))) throw std::runtime_error("height must be a power of two");
-    dims.push_back(Dim{widths[i], heights[i]});
-    max_h = std::max(max_h, heights[i]);
-    row_words += widths[i];
-  }
-  if (dims.empty()) throw std::runtime_error("msbb_mmcs_verify_batch: no matrices");
-  const unsigned log_max = log2_strict(max_h);
-  if (cap_height > log_max) throw std::runtime_error("msbb_mmcs_verify_batch: cap_height above log2 of the tallest matrix");
-  const size_t path_len = log_max - cap_height, capn = size_t(1) << cap_height;
-  bool cap_ok = true;
-  for (size_t c = 0; c < 8 * capn; c++) cap_ok = cap_ok && cap[c] < BB_P;
-  PathPlan pl;
-  if (!cap_ok || !mmcs_plan(dims, capn, path_len, pl)) {  // a non-canonical cap equals no digest; a matrix shorter than the cap layer is
-    memset(ok_out, 0, n_openings);                        // never reached by the walk: MerkleTreeMmcs refuses every opening
-    return;
-  }
-  std::vector<size_t> col0(dims.size());  // where each matrix's row starts in an opening's values
-  for (size_t i = 0, at = 0; i < dims.size(); i++) col0[i] = at, at += dims[i].w;
-  auto canonical = [&](size_t k) {
-    bool ok = indices[k] < max_h;
-    const u32* v = vals + k * row_words;
-    for (size_t c = 0; c < row_words && ok; c++) ok = v[c] < BB_P;
-    const u32* s = siblings + k * path_len * 8;
-    for (size_t c = 0; c < path_len * 8 && ok; c++) ok = s[c] < BB_P;
-    return ok;
-  };
-  std::vector<u32> fail;
-  size_t k0 = 0;
-  while (k0 < n_openings) {
-    BVBatch B;
-    const u32 cap_off = 0, grp_off = 0;
-    B.digs.resize(capn);
-    for (size_t c = 0; c < 8 * capn; c++) B.digs[c / 8].w[c % 8] = bb_to_monty(cap[c]);
-    B.u32s = pl.groups;
-    size_t k = k0;
-    for (; k < n_openings && B.bytes() <= BV_FLUSH_BYTES; k++) {
-      if (!canonical(k)) continue;  // refused here; ok_out is set below
-      const u32* v = vals + k * row_words;
-      const u64 vals_off = B.words.size();
-      for (size_t i : pl.order)
-        for (size_t c = 0; c < dims[i].w; c++) B.words.push_back(bb_to_monty(v[col0[i] + c]));
-      const u32 sib = (u32)B.digs.size();
-      B.digs.resize(sib + path_len);
-      const u32* s = siblings + k * path_len * 8;
-      for (size_t c = 0; c < path_len * 8; c++) B.digs[sib + c / 8].w[c % 8] = bb_to_monty(s[c]);
-      bv_add_item(B, pl, vals_off, false, indices[k], sib, cap_off, grp_off, (u32)(k - k0));
-    }
-    B.n_flags = k - k0;
-    bvbatch_run(ctx, d_perm, B, fail);
-    for (size_t j = k0; j < k; j++) ok_out[j] = canonical(j) && !fail[j - k0] ? 1 : 0;
-    k0 = k;
-  }
-}
 
 }  // namespace msbb
 
@@ -2682,7 +1411,7 @@ int32_t msbb_challenger_observe_digests(msbb_challenger* ch, const uint32_t* dig
 int32_t msbb_challenger_sample_ext(msbb_challenger* ch, uint32_t out4[4]) {
   BB_TRY
   if (!ch || !out4) throw std::runtime_error("null argument");
-  e4_out(ch->ch->sample_e4(), out4);
+  e4_out(ch->ch->sample_ext(), out4);
   return MS_OK;
   BB_CATCH
 }

@@ -1,64 +1,25 @@
 // Device side of batched verification for the BabyBear / Poseidon2 configuration (msbb_verify_batch,
-// msbb_mmcs_verify_batch): the flat arrays the host builds from proofs whose shape it has already checked, and the bodies
-// of the two kernels that consume them. No kernel ever sees proof bytes: every offset and length below is derived from
-// lengths bb_prover.hip has validated. The bodies are __host__ __device__ like the field functions of bb_dev.h they are
-// written with, so the same text can be run on the host against pcs_verify (one "thread" per call).
+// msbb_mmcs_verify_batch): the BabyBear instance of the flat arrays of verify_batch.h, which the host builds from proofs whose
+// shape it has already checked, and the bodies of the two kernels that consume them. No kernel ever sees proof bytes: every
+// offset and length is derived from lengths the collector of verify_batch.h has validated. The bodies are __host__ __device__
+// like the field functions of bb_dev.h they are written with, so the same text can be run on the host against
+// bb_verifier.hip::pcs_verify (one "thread" per call).
 #pragma once
 #include "bb_dev.h"
+#include "verify_batch.h"
 
 namespace msbb {
 
-// MerkleTreeMmcs::verify_batch of one opening. The rows lie in walk order (stable sort by descending height) at
-// words[vals_off ..); u32s[grp_off + k], k = 0 .. n_levels, is 1 + the word count of the matrices whose height is
-// max_height >> k (0: none at that level; entry 0 is the leaf and always present).
-struct BVPathItem {
-  u64 vals_off, index;
-  u32 sib_off;   // digs: n_levels siblings, bottom-up
-  u32 cap_off;   // digs: the cap; entry index >> n_levels is compared
-  u32 grp_off, n_levels;
-  u32 flag;      // fail[flag] |= 1 when the opening is refused
-  u32 fri_row;   // host side only: vals_off counts from the FRI leaf rows (resolved before the upload)
-};
-
-struct BVMatDesc {
-  u32 row_off;   // words from the query's block to this matrix's opened row
-  u32 width, n_points;
-  u32 pv_off;    // ext: per point its z, then `width` claimed values
-};
-struct BVHeightDesc {
-  u32 lh;        // log2 of the LDE height
-  u32 mat_off, n_mats;  // mats: the matrices of this height in round -> matrix order
-  u32 pad;
-};
-// one proof's query arithmetic; every query of the proof is one thread
-struct BVProofDesc {
-  E4 alpha;
-  u64 blk_off, blk_stride;  // words: per query its index, then the opened input rows
-  u64 fri_off, fri_stride;  // words: per query the FRI leaf rows, written by the arithmetic kernel for the path kernel
-  u64 ro_off;               // ro: per query n_heights reduced openings (scratch of the arithmetic kernel)
-  u32 sib_off, sib_stride;  // ext: per query the FRI sibling values of all rounds
-  u32 beta_off;             // ext: one beta per round
-  u32 final_off, n_final;   // ext: the final polynomial
-  u32 arity_off;            // u32s: log_arity per round
-  u32 height_off, n_heights;  // heights, descending; the first is log_gmax
-  u32 zero_slot;            // the height whose reduced opening must vanish (always the last one), or ~0
-  u32 n_rounds, log_gmax, query0, flag;
-};
-
-struct BVDev {
-  const BVPathItem* items;
-  const BVProofDesc* proofs;
-  const BVMatDesc* mats;
-  const BVHeightDesc* heights;
-  const u32* u32s;
-  const u32* qmap;     // global query -> proof descriptor
-  const E4* ext;
-  const Digest8* digs;
-  u32* fail;
-  u32* words;          // uploaded words (Montgomery form, as they stand in the proof), then the FRI leaf rows
-  E4* ro;
+using BVPathItem = msamd::VPathItem;
+using BVMatDesc = msamd::VMatDesc;
+using BVHeightDesc = msamd::VHeightDesc;
+using BVProofDesc = msamd::VProofDesc<E4>;
+// words in Montgomery form, as they stand in the proof
+struct BVDev : msamd::VDev<u32, E4, Digest8> {
   const Poseidon2* perm;  // the system's (or the context's) round constants, already in device memory
 };
+static_assert(sizeof(BVProofDesc) == 112 && std::is_trivially_copyable<BVProofDesc>::value, "BVProofDesc layout");
+static_assert(sizeof(BVDev) == 96 && std::is_trivially_copyable<BVDev>::value, "BVDev layout");
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define BBV_FLAG_OR(p, v) atomicOr((p), (v))
@@ -134,7 +95,7 @@ BB_HD void bbv_path_body(const BVDev& d, u32 t) {
   if (diff) BBV_FLAG_OR(d.fail + it.flag, 1u);
 }
 
-// one query of one proof: bbv_queries_k's thread t. The arithmetic of bb_prover.hip::pcs_verify's query loop.
+// one query of one proof: bbv_queries_k's thread t. The arithmetic of bb_verifier.hip::pcs_verify's query loop.
 BB_HD void bbv_query_body(const BVDev& d, u32 t) {
   const BVProofDesc& P = d.proofs[d.qmap[t]];
   const u32 q = t - P.query0;

@@ -1,6 +1,6 @@
 // Kernels of batched verification for the BabyBear / Poseidon2 configuration (bb_verify_dev.h). Two launches per batch:
 //   bbv_queries_k  one thread per (proof, query): reduced openings, FRI fold chain, final polynomial - the per-query
-//                  arithmetic of bb_prover.hip::pcs_verify restated with the same field functions (bb_dev.h is shared by
+//                  arithmetic of bb_verifier.hip::pcs_verify restated with the same field functions (bb_dev.h is shared by
 //                  host and device, so the results are the same field elements). Writes every FRI round's leaf row.
 //   bbv_paths_k    one thread per Merkle path (input rounds, FRI rounds, msbb_mmcs_verify_batch openings): a dependent
 //                  chain of Poseidon2 permutations per thread, wide across threads (leaf_hash_k in bb_kernels.hip is the

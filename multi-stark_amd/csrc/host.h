@@ -47,6 +47,12 @@ struct Challenger {
   E2 sample_ext();
   size_t sample_bits(unsigned bits);
   u64 grind(unsigned bits);
+  bool check_witness(unsigned bits, u64 w) {
+    if (bits == 0) return true;  // DeterministicPow: nothing is observed at zero bits (src/types.rs:75-80)
+    if (w >= GL_P) return false;
+    observe(w);
+    return sample_bits(bits) == 0;
+  }
 };
 
 struct Params {

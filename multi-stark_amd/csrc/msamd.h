@@ -115,7 +115,7 @@ struct Ctx {
   // address in round 4's fuzzing)
   uint8_t* bounce = nullptr;
   static constexpr size_t BOUNCE_BYTES = size_t(4) << 20;
-  // page-locked staging of batched verification (verifier.hip): a whole batch's arrays go up in ONE asynchronous copy, so
+  // page-locked staging of batched verification (verify_batch.h): a whole batch's arrays go up in ONE asynchronous copy, so
   // the number of host waits of ms_verify_batch does not grow with the batch. Grows on demand, reused by later calls.
   uint8_t* verify_stage = nullptr;
   size_t verify_stage_cap = 0;

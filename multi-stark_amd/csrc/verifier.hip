@@ -19,8 +19,6 @@ namespace msamd {
 
 namespace {
 
-enum : int { V_OK = 0, V_INVALID_OPENING = 2, V_INVALID_SHAPE = 3, V_INVALID_SYSTEM = 4, V_OOD_MISMATCH = 5, V_UNBALANCED = 6 };
-
 struct Malformed {};  // thrown by the reader: truncated or oversized fields -> InvalidProofShape
 
 struct Reader {
@@ -191,9 +189,6 @@ Digest compress2(const Digest& l, const Digest& r) {
 }
 bool same(const Digest& a, const Digest& b) { return memcmp(a.b, b.b, 32) == 0; }
 
-struct Dim {
-  size_t w, h;
-};
 // MerkleTreeMmcs::verify_batch: rows of the tallest matrices form the leaf, shorter ones are injected on the way up
 bool mmcs_verify_batch(const std::vector<Digest>& cap, const std::vector<Dim>& dims, size_t index, const BatchOpening& o) {
   if (dims.size() != o.rows.size() || dims.empty()) return false;
@@ -232,51 +227,52 @@ bool mmcs_verify_batch(const std::vector<Digest>& cap, const std::vector<Dim>& d
   return same(root, cap[idx]);
 }
 
-bool check_witness(Challenger& ch, unsigned bits, u64 w) {
-  if (bits == 0) return true;  // DeterministicPow: nothing is observed at zero bits (src/types.rs:75-80)
-  if (w >= GL_P) return false;
-  ch.observe(w);
-  return ch.sample_bits(bits) == 0;
-}
-
 struct RoundClaim {
   std::vector<Digest> commit;
   std::vector<unsigned> log_n;                                       // per matrix: log2 of the trace height
   std::vector<std::vector<std::pair<E2, const std::vector<E2>*>>> mats;  // per matrix: (point, claimed values)
 };
 
+struct Prepared;
+int verify_prepare(HSystem& sys, size_t n_claims, const u64* claim_offsets, const u64* claim_data, const uint8_t* proof_bytes, size_t proof_len,
+                   Prepared& P);
+int verify_ood(const HSystem& sys, const Prepared& P);
+
+// The Goldilocks / BLAKE3 configuration as verify_batch.h wants a field described
+struct GlVerify {
+  using Word = u64;
+  using Ext = E2;
+  using Dig = Digest;
+  using Dev = GVDev;
+  static constexpr unsigned ext_words = 2;
+  static constexpr unsigned two_adicity = GL_TWO_ADICITY;  // gl_two_adic_generator is defined up to 2^32
+  // Rows of one height are hashed together, inside a thread with a chunk stack held in registers (verify_dev.h): a wider group
+  // cannot go to the device. ms_verify_batch checks the system's trace widths against it before anything else - the system
+  // bounds how wide such a group can be, whatever a proof says - and ms_mmcs_verify_batch reports PLAN_TOO_WIDE as an error.
+  static constexpr u32 max_group_words = VB_MAX_GROUP_WORDS;
+  // A matrix opened at no point (the others are bound to the opened values) whose row has another width in a later query:
+  // BLAKE3 takes the length in, so the row could not hash to the same commitment, which is how pcs_verify refuses it.
+  static constexpr int unopened_width_mismatch = COLLECT_REFUSED;
+  static void launch(Ctx& ctx, const Dev& d, size_t n_queries, size_t n_items, double path_bytes) {
+    verify_batch_launch(ctx, d, n_queries, n_items, path_bytes);
+  }
+  // the host side of one proof (verify_batch_run)
+  using Prepared = ::msamd::Prepared;
+  static constexpr auto prepare = verify_prepare;
+  static constexpr auto ood = verify_ood;
+  static const FriProofV& fri(const Prepared& P);
+  static bool pcs_verify(const HSystem& sys, const Prepared& P, Challenger& ch);
+};
+
 bool pcs_verify(const Params& prm, const std::vector<RoundClaim>& rounds, const FriProofV& proof, Challenger& ch) {
   const unsigned lb = (unsigned)prm.log_blowup;
-  for (auto& r : rounds)
-    for (auto& m : r.mats)
-      for (auto& pv : m)
-        for (auto& y : *pv.second) ch.observe_ext(y);
-  const E2 alpha = ch.sample_ext();
-  const size_t nrounds = proof.commits.size();
-  if (proof.pow.size() != nrounds) return false;
-  // every query repeats the rounds' arities; the first one's place the tallest input, and each is checked below against
-  // what the prover had to choose (p3-fri compute_log_arity_for_round) once the input heights are known
-  std::vector<unsigned> arities(nrounds, 1);
-  if (!proof.queries.empty()) {
-    if (proof.queries[0].steps.size() != nrounds) return false;
-    for (size_t i = 0; i < nrounds; i++) arities[i] = proof.queries[0].steps[i].log_arity;
-  }
-  unsigned log_gmax = (unsigned)(lb + prm.log_final_poly_len);
-  for (unsigned a : arities) {
-    if (a > prm.max_log_arity) return false;
-    log_gmax += a;
-  }
-  if (log_gmax > GL_TWO_ADICITY) return false;  // no subgroup of that order: gl_two_adic_generator is defined up to 2^32
-  std::vector<E2> betas;
-  for (size_t i = 0; i < nrounds; i++) {
-    ch.observe_cap(proof.commits[i]);
-    if (!check_witness(ch, (unsigned)prm.commit_pow_bits, proof.pow[i])) return false;
-    betas.push_back(ch.sample_ext());
-  }
-  if (proof.final_poly.size() != (size_t(1) << prm.log_final_poly_len)) return false;
-  for (auto& c : proof.final_poly) ch.observe_ext(c);
-  if (proof.queries.size() != prm.num_queries) return false;
-  if (!check_witness(ch, (unsigned)prm.query_pow_bits, proof.query_pow)) return false;
+  FriReplay<E2> fr;
+  if (!fri_replay<GlVerify>(prm, rounds, proof, ch, fr)) return false;
+  const E2 alpha = fr.alpha;
+  const std::vector<unsigned>& arities = fr.arities;
+  const std::vector<E2>& betas = fr.betas;
+  const unsigned log_gmax = fr.log_gmax;
+  const size_t nrounds = arities.size();
   const unsigned log_final_height = (unsigned)(lb + prm.log_final_poly_len);
   for (auto& qp : proof.queries) {
     const size_t index = ch.sample_bits(log_gmax);
@@ -457,7 +453,7 @@ struct Prepared {
   E2 beta, gamma, acc, alpha, zeta;
   std::vector<RoundClaim> rounds;
   Challenger ch;
-  explicit Prepared(const std::vector<uint8_t>& seed) : ch(seed) {}
+  explicit Prepared(const HSystem& sys) : ch(sys.seed) {}
 };
 
 // parse, verify_shape and the transcript replay: V_OK, or the verdict that ends the verification here
@@ -719,7 +715,7 @@ int verify_ood(const HSystem& sys, const Prepared& P) {
 
 int verify(HSystem& sys, size_t n_claims, const u64* claim_offsets, const u64* claim_data, const uint8_t* proof_bytes, size_t proof_len) {
   HIP_CHECK(hipSetDevice(sys.ctx->device));
-  Prepared P(sys.seed);
+  Prepared P(sys);
   const int v = verify_prepare(sys, n_claims, claim_offsets, claim_data, proof_bytes, proof_len, P);
   if (v != V_OK) return v;
   if (!pcs_verify(sys.params, P.rounds, P.proof.fri, P.ch)) return V_INVALID_OPENING;
@@ -727,407 +723,22 @@ int verify(HSystem& sys, size_t n_claims, const u64* claim_offsets, const u64* c
 }
 
 // ---------------------------------------------------------------- batched verification (ms_verify_batch, ms_mmcs_verify_batch)
-// The host keeps what is serial or cheap - parsing, verify_shape, the transcript replay, both proof-of-work checks, the query
-// indices, the arity schedule and the out-of-domain check - and makes EVERY structural check of pcs_verify before a value is
-// read. What remains per query (reduced openings, fold chain, final polynomial) and per Merkle path goes to the device as flat
-// arrays whose offsets all come from the lengths validated here (verify_dev.h); a proof refused on the host adds nothing to them.
+// the collector and the flush loop are verify_batch.h's, instantiated with GlVerify
 namespace {
-
-struct VBatch {
-  std::vector<u64> words;
-  std::vector<E2> ext;
-  std::vector<Digest> digs;
-  std::vector<u32> u32s, qmap;
-  std::vector<VPathItem> items;
-  std::vector<VProofDesc> proofs;
-  std::vector<VMatDesc> mats;
-  std::vector<VHeightDesc> heights;
-  size_t n_flags = 0, fri_words = 0, ro_count = 0;
-  double path_bytes = 0;
-  size_t bytes() const {
-    return words.size() * 8 + ext.size() * 16 + digs.size() * 32 + (u32s.size() + qmap.size()) * 4 + items.size() * sizeof(VPathItem) +
-           fri_words * 8 + ro_count * 16;
-  }
-};
-static const size_t VB_FLUSH_BYTES = size_t(256) << 20;  // a batch larger than this goes to the device in several parts
-
-enum { PLAN_OK = 0, PLAN_REFUSED, PLAN_TOO_WIDE };
-struct PathPlan {
-  std::vector<size_t> order;  // the matrices in walk order: stable by descending height
-  std::vector<u32> groups;    // per level 0 .. path_len: 1 + words of the matrices of height max >> level, 0 = none
-  unsigned log_max = 0;
-};
-// everything mmcs_verify_batch refuses without hashing, and the walk order of what it would hash
-int mmcs_plan(const std::vector<Dim>& dims, size_t capn, size_t path_len, PathPlan& pl) {
-  if (dims.empty()) return PLAN_REFUSED;
-  pl.order.resize(dims.size());
-  for (size_t i = 0; i < dims.size(); i++) {
-    pl.order[i] = i;
-    if (dims[i].h == 0 || (dims[i].h & (dims[i].h - 1))) return PLAN_REFUSED;
-  }
-  std::stable_sort(pl.order.begin(), pl.order.end(), [&](size_t a, size_t b) { return dims[a].h > dims[b].h; });
-  pl.log_max = log2_strict(dims[pl.order[0]].h);
-  if (capn == 0 || (capn & (capn - 1))) return PLAN_REFUSED;
-  const unsigned ch = log2_strict(capn);
-  if (ch > pl.log_max || path_len != pl.log_max - ch) return PLAN_REFUSED;
-  std::vector<u64> gw(path_len + 1, 0);
-  std::vector<uint8_t> present(path_len + 1, 0);
-  for (size_t i : pl.order) {
-    const size_t k = pl.log_max - log2_strict(dims[i].h);
-    if (k > path_len) return PLAN_REFUSED;  // shorter than the cap layer: never injected (pos != order.size())
-    gw[k] += dims[i].w;
-    present[k] = 1;
-  }
-  pl.groups.assign(path_len + 1, 0);
-  for (size_t k = 0; k <= path_len; k++) {
-    if (gw[k] > VB_MAX_GROUP_WORDS) return PLAN_TOO_WIDE;
-    if (present[k]) pl.groups[k] = 1 + (u32)gw[k];
-  }
-  return PLAN_OK;
-}
-
-template <class T>
-size_t vb_place(size_t& off, size_t count) {
-  off = (off + 63) & ~size_t(63);
-  const size_t at = off;
-  off += count * sizeof(T);
-  return at;
-}
-
-// upload, two launches, one read-back: fail[flag] != 0 where a device check of that flag's owner failed
-void vbatch_run(Ctx& ctx, VBatch& B, std::vector<u32>& fail) {
-  fail.assign(B.n_flags, 0);
-  if (B.items.empty() && B.qmap.empty()) return;
-  for (auto& it : B.items)
-    if (it.pad) {  // a FRI leaf row: lives behind the uploaded words
-      it.vals_off += B.words.size();
-      it.pad = 0;
-    }
-  for (auto& p : B.proofs) p.fri_off += B.words.size();
-  size_t off = 0;
-  const size_t at_items = vb_place<VPathItem>(off, B.items.size()), at_proofs = vb_place<VProofDesc>(off, B.proofs.size());
-  const size_t at_mats = vb_place<VMatDesc>(off, B.mats.size()), at_heights = vb_place<VHeightDesc>(off, B.heights.size());
-  const size_t at_u32s = vb_place<u32>(off, B.u32s.size()), at_qmap = vb_place<u32>(off, B.qmap.size());
-  const size_t at_ext = vb_place<E2>(off, B.ext.size()), at_digs = vb_place<Digest>(off, B.digs.size());
-  const size_t at_fail = vb_place<u32>(off, B.n_flags), at_words = vb_place<u64>(off, B.words.size());
-  const size_t up = off;
-  off += B.fri_words * 8;
-  const size_t at_ro = vb_place<E2>(off, B.ro_count);
-  size_t total = 4096;
-  while (total < off) total <<= 1;  // few distinct sizes: the context's pool keeps blocks by exact size
-  if (ctx.verify_stage_cap < up) {
-    HIP_CHECK(hipStreamSynchronize(ctx.stream));
-    if (ctx.verify_stage) (void)hipHostFree(ctx.verify_stage);
-    ctx.verify_stage = nullptr;
-    ctx.verify_stage_cap = 0;
-    size_t cap = size_t(1) << 20;
-    while (cap < up) cap <<= 1;
-    HIP_CHECK(hipHostMalloc((void**)&ctx.verify_stage, cap, hipHostMallocDefault));
-    ctx.verify_stage_cap = cap;
-  }
-  uint8_t* st = ctx.verify_stage;
-  auto put = [&](size_t at, const void* src, size_t n) {
-    if (n) memcpy(st + at, src, n);
-  };
-  put(at_items, B.items.data(), B.items.size() * sizeof(VPathItem));
-  put(at_proofs, B.proofs.data(), B.proofs.size() * sizeof(VProofDesc));
-  put(at_mats, B.mats.data(), B.mats.size() * sizeof(VMatDesc));
-  put(at_heights, B.heights.data(), B.heights.size() * sizeof(VHeightDesc));
-  put(at_u32s, B.u32s.data(), B.u32s.size() * 4);
-  put(at_qmap, B.qmap.data(), B.qmap.size() * 4);
-  put(at_ext, B.ext.data(), B.ext.size() * sizeof(E2));
-  put(at_digs, B.digs.data(), B.digs.size() * sizeof(Digest));
-  memset(st + at_fail, 0, B.n_flags * 4);
-  put(at_words, B.words.data(), B.words.size() * 8);
-  DBuf<uint8_t> dev(ctx, total);
-  HIP_CHECK(hipMemcpyAsync(dev.p, st, up, hipMemcpyHostToDevice, ctx.stream));
-  VDev d;
-  d.items = (const VPathItem*)(dev.p + at_items);
-  d.proofs = (const VProofDesc*)(dev.p + at_proofs);
-  d.mats = (const VMatDesc*)(dev.p + at_mats);
-  d.heights = (const VHeightDesc*)(dev.p + at_heights);
-  d.u32s = (const u32*)(dev.p + at_u32s);
-  d.qmap = (const u32*)(dev.p + at_qmap);
-  d.ext = (const E2*)(dev.p + at_ext);
-  d.digs = (const Digest*)(dev.p + at_digs);
-  d.fail = (u32*)(dev.p + at_fail);
-  d.words = (u64*)(dev.p + at_words);
-  d.ro = (E2*)(dev.p + at_ro);
-  verify_batch_launch(ctx, d, B.qmap.size(), B.items.size(), B.path_bytes);
-  ctx.d2h(fail.data(), d.fail, B.n_flags * 4);  // the call's one host wait
-}
-
-void vb_add_item(VBatch& B, const PathPlan& pl, u64 vals_off, bool fri_row, u64 index, u32 sib_off, u32 cap_off, u32 grp_off, u32 flag) {
-  VPathItem it;
-  it.vals_off = vals_off;
-  it.index = index;
-  it.sib_off = sib_off;
-  it.cap_off = cap_off;
-  it.grp_off = grp_off;
-  it.n_levels = (u32)(pl.groups.size() - 1);
-  it.flag = flag;
-  it.pad = fri_row ? 1 : 0;  // resolved by vbatch_run
-  B.items.push_back(it);
-  double w = 0;
-  for (u32 g : pl.groups) w += g ? g - 1 : 0;
-  B.path_bytes += 8 * w + 32.0 * (it.n_levels + 1);
-}
-
-// pcs_verify with the per-query arithmetic and the Merkle paths left to the device: false = refused here (nothing was added
-// to B), true = the verdict is B's flag `flag` after vbatch_run. Widths are fixed by the first query: a later query whose row
-// has another width (only a matrix opened at no point can, the others are bound to the opened values) could not hash to
-// the same commitment, which is how pcs_verify refuses it.
-bool pcs_collect(const Params& prm, const std::vector<RoundClaim>& rounds, const FriProofV& proof, Challenger& ch, VBatch& B, u32 flag) {
-  const unsigned lb = (unsigned)prm.log_blowup;
-  for (auto& r : rounds)
-    for (auto& m : r.mats)
-      for (auto& pv : m)
-        for (auto& y : *pv.second) ch.observe_ext(y);
-  const E2 alpha = ch.sample_ext();
-  const size_t nrounds = proof.commits.size();
-  if (proof.pow.size() != nrounds) return false;
-  std::vector<unsigned> arities(nrounds, 1);
-  if (!proof.queries.empty()) {
-    if (proof.queries[0].steps.size() != nrounds) return false;
-    for (size_t i = 0; i < nrounds; i++) arities[i] = proof.queries[0].steps[i].log_arity;
-  }
-  unsigned log_gmax = (unsigned)(lb + prm.log_final_poly_len);
-  for (unsigned a : arities) {
-    if (a > prm.max_log_arity) return false;
-    log_gmax += a;
-  }
-  if (log_gmax > GL_TWO_ADICITY) return false;
-  std::vector<E2> betas;
-  for (size_t i = 0; i < nrounds; i++) {
-    ch.observe_cap(proof.commits[i]);
-    if (!check_witness(ch, (unsigned)prm.commit_pow_bits, proof.pow[i])) return false;
-    betas.push_back(ch.sample_ext());
-  }
-  if (proof.final_poly.size() != (size_t(1) << prm.log_final_poly_len)) return false;
-  for (auto& c : proof.final_poly) ch.observe_ext(c);
-  if (proof.queries.size() != prm.num_queries) return false;
-  if (!check_witness(ch, (unsigned)prm.query_pow_bits, proof.query_pow)) return false;
-  const unsigned log_final_height = (unsigned)(lb + prm.log_final_poly_len);
-  const size_t nq = proof.queries.size(), R = rounds.size();
-  if (nq == 0) return true;  // nothing is queried: pcs_verify accepts here as well
-  std::vector<size_t> index(nq);
-  for (size_t q = 0; q < nq; q++) index[q] = ch.sample_bits(log_gmax);
-
-  // ---- the input rounds' structure, from the first query
-  struct RoundPlan {
-    PathPlan pl;
-    unsigned log_bmax = 0;
-    std::vector<size_t> width, row_off;  // per matrix: words, and where its row lies in a query's block
-    size_t words = 0, path_len = 0;
-  };
-  std::vector<RoundPlan> rp(R);
-  const QueryProof& q0 = proof.queries[0];
-  if (q0.inputs.size() != R) return false;
-  size_t blk = 1;  // word 0 of a query's block is its index
-  std::map<unsigned, std::vector<std::pair<size_t, size_t>>, std::greater<unsigned>> by_height;  // (round, matrix) in ro's order
-  for (size_t ri = 0; ri < R; ri++) {
-    const RoundClaim& r = rounds[ri];
-    const BatchOpening& bo = q0.inputs[ri];
-    RoundPlan& P = rp[ri];
-    if (bo.rows.size() != r.mats.size()) return false;
-    std::vector<Dim> dims;
-    for (size_t mi = 0; mi < r.mats.size(); mi++) {
-      dims.push_back(Dim{bo.rows[mi].size(), size_t(1) << (r.log_n[mi] + lb)});
-      P.log_bmax = std::max(P.log_bmax, r.log_n[mi] + lb);
-      P.width.push_back(bo.rows[mi].size());
-      for (auto& pv : r.mats[mi])
-        if (pv.second->size() != bo.rows[mi].size()) return false;
-      by_height[r.log_n[mi] + lb].push_back({ri, mi});
-    }
-    if (P.log_bmax > log_gmax) return false;
-    P.path_len = bo.path.size();
-    if (mmcs_plan(dims, r.commit.size(), P.path_len, P.pl) != PLAN_OK) return false;
-    P.row_off.resize(dims.size());
-    for (size_t i : P.pl.order) {
-      P.row_off[i] = blk + P.words;
-      P.words += dims[i].w;
-    }
-    blk += P.words;
-  }
-  // ---- heights of the reduced openings, descending, and the fold chain's schedule
-  std::vector<unsigned> hs;
-  for (auto& kv : by_height) hs.push_back(kv.first);
-  const bool zero_rule = by_height.count(lb) && log_final_height >= lb && lb < log_gmax;  // lb is the lowest height: the last slot
-  const size_t n_chain = hs.size() - (zero_rule ? 1 : 0);
-  if (n_chain == 0 || hs[0] != log_gmax) return false;
-  struct StepPlan {
-    PathPlan pl;
-    size_t path_len = 0, row_off = 0, sib_off = 0;
-    unsigned shift = 0;  // the round's row index is the query index >> shift
-  };
-  std::vector<StepPlan> sp(nrounds);
-  size_t fri_stride = 0, sib_stride = 0;
-  {
-    size_t hp = 1;
-    unsigned lh = log_gmax, shift = 0;
-    for (size_t i = 0; i < nrounds; i++) {
-      const unsigned la = arities[i];
-      if (lh <= log_final_height) return false;
-      unsigned want = std::min<unsigned>((unsigned)prm.max_log_arity, lh - log_final_height);
-      if (hp < n_chain) want = std::min(want, lh - hs[hp]);
-      if (la != want) return false;
-      lh -= la;
-      shift += la;
-      const size_t m = size_t(1) << la;
-      sp[i].path_len = q0.steps[i].path.size();
-      sp[i].shift = shift;
-      sp[i].row_off = fri_stride;
-      sp[i].sib_off = sib_stride;
-      if (mmcs_plan({Dim{2 * m, size_t(1) << lh}}, proof.commits[i].size(), sp[i].path_len, sp[i].pl) != PLAN_OK) return false;
-      fri_stride += 2 * m;
-      sib_stride += m - 1;
-      if (hp < n_chain && hs[hp] == lh) hp++;
-    }
-    if (hp != n_chain) return false;
-  }
-  // ---- every query has that structure
-  for (auto& qp : proof.queries) {
-    if (qp.inputs.size() != R || qp.steps.size() != nrounds) return false;
-    for (size_t ri = 0; ri < R; ri++) {
-      const BatchOpening& bo = qp.inputs[ri];
-      if (bo.rows.size() != rp[ri].width.size() || bo.path.size() != rp[ri].path_len) return false;
-      for (size_t mi = 0; mi < bo.rows.size(); mi++)
-        if (bo.rows[mi].size() != rp[ri].width[mi]) return false;
-    }
-    for (size_t i = 0; i < nrounds; i++) {
-      const FriStep& st = qp.steps[i];
-      if (st.log_arity != arities[i] || st.siblings.size() != (size_t(1) << arities[i]) - 1 || st.path.size() != sp[i].path_len) return false;
-    }
-  }
-
-  // ---- accepted so far: append
-  VProofDesc D;
-  memset(&D, 0, sizeof(D));
-  D.alpha = alpha;
-  D.blk_off = B.words.size();
-  D.blk_stride = blk;
-  D.fri_off = B.fri_words;  // (vbatch_run adds the uploaded words in front)
-  D.fri_stride = fri_stride;
-  D.ro_off = B.ro_count;
-  D.sib_stride = (u32)sib_stride;
-  D.n_rounds = (u32)nrounds;
-  D.log_gmax = log_gmax;
-  D.query0 = (u32)B.qmap.size();
-  D.flag = flag;
-  D.n_heights = (u32)hs.size();
-  D.zero_slot = zero_rule ? (u32)(hs.size() - 1) : ~u32(0);
-  D.height_off = (u32)B.heights.size();
-  for (unsigned lh : hs) {
-    auto& list = by_height[lh];
-    VHeightDesc H;
-    H.lh = lh;
-    H.mat_off = (u32)B.mats.size();
-    H.n_mats = (u32)list.size();
-    H.pad = 0;
-    B.heights.push_back(H);
-    for (auto& rm : list) {
-      const auto& pts = rounds[rm.first].mats[rm.second];
-      VMatDesc M;
-      M.row_off = (u32)rp[rm.first].row_off[rm.second];
-      M.width = (u32)rp[rm.first].width[rm.second];
-      M.n_points = (u32)pts.size();
-      M.pv_off = (u32)B.ext.size();
-      B.mats.push_back(M);
-      for (auto& pv : pts) {
-        B.ext.push_back(pv.first);
-        B.ext.insert(B.ext.end(), pv.second->begin(), pv.second->end());
-      }
-    }
-  }
-  D.beta_off = (u32)B.ext.size();
-  B.ext.insert(B.ext.end(), betas.begin(), betas.end());
-  D.final_off = (u32)B.ext.size();
-  D.n_final = (u32)proof.final_poly.size();
-  B.ext.insert(B.ext.end(), proof.final_poly.begin(), proof.final_poly.end());
-  D.arity_off = (u32)B.u32s.size();
-  for (unsigned a : arities) B.u32s.push_back(a);
-  std::vector<u32> grp_in(R), cap_in(R), grp_fri(nrounds), cap_fri(nrounds);
-  for (size_t ri = 0; ri < R; ri++) {
-    grp_in[ri] = (u32)B.u32s.size();
-    B.u32s.insert(B.u32s.end(), rp[ri].pl.groups.begin(), rp[ri].pl.groups.end());
-    cap_in[ri] = (u32)B.digs.size();
-    B.digs.insert(B.digs.end(), rounds[ri].commit.begin(), rounds[ri].commit.end());
-  }
-  for (size_t i = 0; i < nrounds; i++) {
-    grp_fri[i] = (u32)B.u32s.size();
-    B.u32s.insert(B.u32s.end(), sp[i].pl.groups.begin(), sp[i].pl.groups.end());
-    cap_fri[i] = (u32)B.digs.size();
-    B.digs.insert(B.digs.end(), proof.commits[i].begin(), proof.commits[i].end());
-  }
-  D.sib_off = (u32)B.ext.size();
-  const u32 proof_slot = (u32)B.proofs.size();
-  for (size_t q = 0; q < nq; q++) {
-    const QueryProof& qp = proof.queries[q];
-    const u64 base = B.words.size();
-    B.words.push_back(index[q]);
-    for (size_t ri = 0; ri < R; ri++) {
-      const BatchOpening& bo = qp.inputs[ri];
-      const u64 vals_off = B.words.size();
-      for (size_t i : rp[ri].pl.order) B.words.insert(B.words.end(), bo.rows[i].begin(), bo.rows[i].end());
-      const u32 sib = (u32)B.digs.size();
-      B.digs.insert(B.digs.end(), bo.path.begin(), bo.path.end());
-      vb_add_item(B, rp[ri].pl, vals_off, false, index[q] >> (log_gmax - rp[ri].log_bmax), sib, cap_in[ri], grp_in[ri], flag);
-    }
-    (void)base;
-    for (size_t i = 0; i < nrounds; i++) {
-      const FriStep& st = qp.steps[i];
-      B.ext.insert(B.ext.end(), st.siblings.begin(), st.siblings.end());
-      const u32 sib = (u32)B.digs.size();
-      B.digs.insert(B.digs.end(), st.path.begin(), st.path.end());
-      vb_add_item(B, sp[i].pl, B.fri_words + q * fri_stride + sp[i].row_off, true, index[q] >> sp[i].shift, sib, cap_fri[i], grp_fri[i], flag);
-    }
-    B.qmap.push_back(proof_slot);
-  }
-  B.fri_words += nq * fri_stride;
-  B.ro_count += nq * hs.size();
-  B.proofs.push_back(D);
-  return true;
-}
-
+const FriProofV& GlVerify::fri(const Prepared& P) { return P.proof.fri; }
+bool GlVerify::pcs_verify(const HSystem& sys, const Prepared& P, Challenger& ch) { return msamd::pcs_verify(sys.params, P.rounds, P.proof.fri, ch); }
 }  // namespace
 
 void verify_batch(HSystem& sys, size_t n_proofs, const u64* n_claims, const u64* const* claim_offsets, const u64* const* claim_data,
                   const uint8_t* const* proofs, const u64* proof_lens, int32_t* verdicts) {
-  Ctx& ctx = *sys.ctx;
-  HIP_CHECK(hipSetDevice(ctx.device));
-  {  // rows of one height are hashed together: the system bounds how wide such a group can be, whatever a proof says
+  {  // GlVerify::max_group_words
     size_t w[4] = {0, 0, 0, 0};
     for (auto& c : sys.circuits) w[0] += c.main_width, w[1] += c.stage2_width, w[2] += c.pre_width, w[3] += 2 * c.quotient_degree();
     for (size_t x : w)
-      if (x > VB_MAX_GROUP_WORDS) throw std::runtime_error("ms_verify_batch: the system's traces are wider than the device verifier hashes in one leaf");
+      if (x > GlVerify::max_group_words)
+        throw std::runtime_error("ms_verify_batch: the system's traces are wider than the device verifier hashes in one leaf");
   }
-  static const u64 no_offsets[1] = {0};
-  VBatch B;
-  std::vector<std::pair<size_t, int>> waiting;  // (proof, its out-of-domain verdict): the device decides between that and 2
-  std::vector<u32> fail;
-  auto flush = [&]() {
-    B.n_flags = waiting.size();
-    vbatch_run(ctx, B, fail);
-    for (size_t k = 0; k < waiting.size(); k++) verdicts[waiting[k].first] = fail[k] ? V_INVALID_OPENING : waiting[k].second;
-    waiting.clear();
-    B = VBatch();
-  };
-  for (size_t i = 0; i < n_proofs; i++) {
-    const u64* offs = n_claims[i] ? claim_offsets[i] : no_offsets;
-    Prepared P(sys.seed);
-    const int v = verify_prepare(sys, (size_t)n_claims[i], offs, claim_data ? claim_data[i] : nullptr, proofs[i], (size_t)proof_lens[i], P);
-    if (v != V_OK) {
-      verdicts[i] = v;
-      continue;
-    }
-    if (!pcs_collect(sys.params, P.rounds, P.proof.fri, P.ch, B, (u32)waiting.size())) {
-      verdicts[i] = V_INVALID_OPENING;
-      continue;
-    }
-    waiting.push_back({i, verify_ood(sys, P)});
-    if (B.bytes() > VB_FLUSH_BYTES) flush();
-  }
-  flush();
+  verify_batch_run<GlVerify>(sys, GVDev(), n_proofs, n_claims, claim_offsets, claim_data, proofs, proof_lens, verdicts);
 }
 
 void mmcs_verify_batch_device(Ctx& ctx, const std::vector<size_t>& heights, const std::vector<size_t>& widths, const uint8_t* cap,
@@ -1148,7 +759,7 @@ void mmcs_verify_batch_device(Ctx& ctx, const std::vector<size_t>& heights, cons
   if (cap_height > log_max) throw std::runtime_error("ms_mmcs_verify_batch: cap_height above log2 of the tallest matrix");
   const size_t path_len = log_max - cap_height, capn = size_t(1) << cap_height;
   PathPlan pl;
-  const int pr = mmcs_plan(dims, capn, path_len, pl);
+  const int pr = mmcs_plan<GlVerify>(dims, capn, path_len, pl);
   if (pr == PLAN_TOO_WIDE) throw std::runtime_error("ms_mmcs_verify_batch: rows of one height wider than the device verifier hashes in one leaf");
   if (pr != PLAN_OK) {  // a matrix shorter than the cap layer is never reached by the walk: MerkleTreeMmcs refuses every opening
     memset(ok_out, 0, n_openings);
@@ -1159,7 +770,7 @@ void mmcs_verify_batch_device(Ctx& ctx, const std::vector<size_t>& heights, cons
   std::vector<u32> fail;
   size_t k0 = 0;
   while (k0 < n_openings) {
-    VBatch B;
+    VBatch<GlVerify> B;
     const u32 cap_off = 0, grp_off = 0;
     B.digs.resize(capn);
     memcpy(B.digs.data(), cap, 32 * capn);
@@ -1178,7 +789,7 @@ void mmcs_verify_batch_device(Ctx& ctx, const std::vector<size_t>& heights, cons
       vb_add_item(B, pl, vals_off, false, indices[k], sib, cap_off, grp_off, (u32)(k - k0));
     }
     B.n_flags = k - k0;
-    vbatch_run(ctx, B, fail);
+    vbatch_run(ctx, GVDev(), B, fail);
     for (size_t j = k0; j < k; j++) {
       bool ok = indices[j] < max_h && !fail[j - k0];
       const u64* v = vals + j * row_words;

@@ -107,7 +107,7 @@ __device__ __forceinline__ void load_digest(const Digest* d, u32 out[8]) {
   out[4] = b.x, out[5] = b.y, out[6] = b.z, out[7] = b.w;
 }
 
-__global__ __launch_bounds__(256) void verify_paths_k(VDev d, u32 n_items) {
+__global__ __launch_bounds__(256) void verify_paths_k(GVDev d, u32 n_items) {
   const u32 t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n_items) return;
   const VPathItem it = d.items[t];
@@ -153,10 +153,10 @@ __global__ __launch_bounds__(256) void verify_paths_k(VDev d, u32 n_items) {
   if (diff) atomicOr(d.fail + it.flag, 1u);
 }
 
-__global__ __launch_bounds__(256) void verify_queries_k(VDev d, u32 n_queries) {
+__global__ __launch_bounds__(256) void verify_queries_k(GVDev d, u32 n_queries) {
   const u32 t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n_queries) return;
-  const VProofDesc& P = d.proofs[d.qmap[t]];
+  const GVProofDesc& P = d.proofs[d.qmap[t]];
   const u32 q = t - P.query0;
   const u64* blk = d.words + P.blk_off + (u64)q * P.blk_stride;
   const u64 index = blk[0];
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void verify_queries_k(VDev d, u32 n_queries) {
 
 }  // namespace
 
-void verify_batch_launch(Ctx& ctx, const VDev& d, size_t n_queries, size_t n_items, double path_bytes) {
+void verify_batch_launch(Ctx& ctx, const GVDev& d, size_t n_queries, size_t n_items, double path_bytes) {
   if (n_queries) {
     hipEvent_t ev = ctx.prof_begin(K_OTHER);
     hipLaunchKernelGGL(verify_queries_k, dim3((unsigned)((n_queries + 255) / 256)), dim3(256), 0, ctx.stream, d, (u32)n_queries);

@@ -232,6 +232,29 @@ def test_valid_other_systems(ctx):
     _check(g, [(c, p)] * 2, [0, 0])
 
 
+def test_unopened_matrix_row_width_differs_between_queries(ctx):
+    """The one proof shape the flat device layout cannot hold (COLLECT_HOST). System: even_odd_inputs() plus the preprocessed
+    byte table of squares_inputs() as a third, inactive circuit (even_odd_inputs(with_dead=True)'s dead circuit has no
+    preprocessed trace), under test_params(). The table's committed matrix is opened at no point, so only its Merkle path
+    binds the row a query shows for it. One zero word is appended to that row in the second query only, and the proof sits
+    between two untouched ones in one call. The padding-free sponge hashes [x] and [x, 0] to one digest, so msbb_verify may
+    accept the proof; whatever it says, the batch says the same (it runs pcs_verify on the host for this proof)."""
+    g = _system(ctx, "evenodd+dead table", fe.test_params(), lambda: fe.even_odd_inputs() + [fe.squares_inputs()[0]])
+    with fe.field(fe.BABYBEAR):
+        traces = fe.even_odd_traces() + [np.zeros((0, 1), dtype=np.uint64)]
+    c, p = _prove(g, traces, [[0, 4, 1]])
+    t = pc.parse(p, 4, 4)
+    assert t["active"] == [1, 1, 0] and t["preprocessed_opened_values"] == [[]]
+    rows = t["opening_proof"]["query_proofs"][1]["input_proof"][-1]["opened_values"]  # the preprocessed round comes last
+    assert [len(r) for r in rows] == [1]
+    rows[0].append(0)
+    items = [(c, p), (c, pc.serialize(t, 4, 4)), (c, p)]
+    got, ref = g.verify_batch(items), [g.verify(ci, pi) for ci, pi in items]
+    print("width-mismatch proof (BabyBear): msbb_verify %d, msbb_verify_batch %d" % (ref[1], got[1]))
+    assert got == ref
+    assert got[0] == 0 and got[2] == 0
+
+
 @pytest.mark.parametrize("name", ["caps_final", "arity2", "arity3", "blowup1"])
 def test_parameter_variants(ctx, name):
     g, c, p = _mul(ctx, name, fe.Params(**VARIANTS[name]), 7)

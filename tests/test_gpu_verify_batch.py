@@ -184,6 +184,26 @@ def test_valid_other_systems(pkg, ctx, oracle, fe):
     _check(g, items, oracle.System(g.blob), [0, 0])
 
 
+def test_unopened_matrix_row_width_differs_between_queries(pkg, ctx, fe):
+    """The one proof shape the flat device layout cannot hold. System: even_odd_inputs() plus the preprocessed byte table of
+    squares_inputs() as a third, inactive circuit (even_odd_inputs(with_dead=True)'s dead circuit has no preprocessed trace),
+    under test_params(). The table's committed matrix is opened at no point, so only its Merkle path binds the row a query
+    shows for it. One zero word is appended to that row in the second query only, and the proof sits between two untouched
+    ones in one call. BLAKE3 takes the length in: the collector refuses on the host what ms_verify refuses by hashing (2)."""
+    g = pkg.System.new(ctx, fe.test_params(), fe.even_odd_inputs() + [fe.squares_inputs()[0]])
+    c, p = _prove(g, fe, fe.even_odd_traces() + [np.zeros((0, 1), dtype=np.uint64)], [[0, 4, 1]])
+    t = pc.parse(p)
+    assert t["active"] == [1, 1, 0] and t["preprocessed_opened_values"] == [[]]
+    rows = t["opening_proof"]["query_proofs"][1]["input_proof"][-1]["opened_values"]  # the preprocessed round comes last
+    assert [len(r) for r in rows] == [1]
+    rows[0].append(0)
+    items = [(c, p), (c, pc.serialize(t)), (c, p)]
+    got, ref = g.verify_batch(items), [g.verify(ci, pi) for ci, pi in items]
+    print("width-mismatch proof (Goldilocks): ms_verify %d, ms_verify_batch %d" % (ref[1], got[1]))
+    assert got == ref
+    assert got[0] == 0 and got[2] == 0
+
+
 VARIANTS = {
     "caps_final": dict(log_blowup=2, cap_height=2, log_final_poly_len=2, num_queries=10, commit_proof_of_work_bits=3, query_proof_of_work_bits=4),
     "arity2": dict(log_blowup=1, cap_height=1, log_final_poly_len=1, max_log_arity=2, num_queries=10, commit_proof_of_work_bits=2,

@@ -1,7 +1,8 @@
-// Host check of the batched BabyBear verifier: the collection (pcs_collect) and both kernel bodies (bb_verify_dev.h) run as
-// host code, one "thread" per call, against verify() on oracle-made proofs and their mutations. CPU only: it is built and
-// run by tools/bb_verify_host_check.py (address and undefined-behaviour sanitizers on), never loaded into Python.
-#include "../multi-stark_amd/csrc/bb_prover.hip"
+// Host check of the batched BabyBear verifier: the collection (verify_batch.h's pcs_collect) and both kernel bodies
+// (bb_verify_dev.h) run as host code, one "thread" per call, against verify() on oracle-made proofs and their mutations. CPU
+// only: it is built and run by tools/bb_verify_host_check.py (address and undefined-behaviour sanitizers on), never loaded
+// into Python.
+#include "../multi-stark_amd/csrc/bb_verifier.hip"
 
 #include <cstdio>
 #include <fstream>
@@ -16,8 +17,9 @@ std::vector<uint8_t> slurp(const std::string& p) {
   return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
 }
 
-// the host half of system_from_blob, for systems without a preprocessed trace
-std::unique_ptr<BSystem> host_system(const std::vector<uint8_t>& blob) {
+// the host half of system_from_blob; the commitment to the preprocessed traces, which the library computes on the device, is
+// the oracle's (canonical words)
+std::unique_ptr<BSystem> host_system(const std::vector<uint8_t>& blob, const std::vector<uint8_t>& pre_commit) {
   Reader rd{blob.data(), blob.size()};
   if (rd.word() != BLOB_MAGIC) throw std::runtime_error("magic");
   std::unique_ptr<BSystem> sys(new BSystem());
@@ -33,12 +35,11 @@ std::unique_ptr<BSystem> host_system(const std::vector<uint8_t>& blob) {
   const u64 ps[7] = {p.log_blowup, p.cap_height, p.log_final_poly_len, p.max_log_arity, p.num_queries, p.commit_pow_bits, p.query_pow_bits};
   for (u64 x : ps) sys->seed.push_back(bb_to_monty((u32)(x % BB_P)));
   const size_t D = 4;
-  size_t nc = rd.word();
+  size_t nc = rd.word(), n_pre = 0;
   for (size_t ci = 0; ci < nc; ci++) {
     sys->circuits.emplace_back();
     BCircuit& c = sys->circuits.back();
     c.main_width = rd.word(), c.pre_width = rd.word(), c.pre_height = rd.word();
-    if (c.pre_width) throw std::runtime_error("host check: no preprocessed traces");
     size_t nn = rd.word(), nz = rd.word(), nl = rd.word();
     c.num_lookups = nl;
     c.stage2_width = std::max<size_t>(nl, 1) * D;
@@ -84,20 +85,35 @@ std::unique_ptr<BSystem> host_system(const std::vector<uint8_t>& blob) {
     }
     c.constraint_count = nz + std::max<size_t>(nl, 1) * D;
     c.max_constraint_degree = std::max(graph_deg, logup_deg);
-    c.pre_height = 0;
-    sys->pre_indices.push_back(-1);
+    if (c.pre_width) {
+      for (size_t i = 0; i < c.pre_height * c.pre_width; i++) rd.word();  // the table itself: only the prover reads it
+      sys->pre_indices.push_back((int)n_pre++);
+    } else {
+      c.pre_height = 0;
+      sys->pre_indices.push_back(-1);
+    }
   }
   if (rd.off != blob.size()) throw std::runtime_error("trailing");
+  if (n_pre) {
+    if (pre_commit.empty() || pre_commit.size() % sizeof(Digest8)) throw std::runtime_error("host check: no preprocessed commitment");
+    sys->has_pre = true;
+    sys->pre_commit.resize(pre_commit.size() / sizeof(Digest8));
+    memcpy(sys->pre_commit.data(), pre_commit.data(), pre_commit.size());
+    for (auto& d : sys->pre_commit)
+      for (u32& w : d.w) w = bb_to_monty(w);
+  }
   return sys;
 }
 
 size_t g_queued = 0, g_dev_fail = 0, g_refused = 0, g_host = 0;
 
-// bvbatch_run with the two kernels as host loops over exactly-sized arrays (an out-of-bounds index is an ASan report)
+typedef msamd::VBatch<BbVerify> BVBatch;
+
+// vbatch_run with the two kernels as host loops over exactly-sized arrays (an out-of-bounds index is an ASan report)
 void run_host(const BSystem& sys, BVBatch& B, std::vector<u32>& fail) {
   fail.assign(B.n_flags, 0);
   if (B.items.empty() && B.qmap.empty()) return;
-  bvbatch_seal(B);
+  msamd::vbatch_seal(B);
   std::vector<u32> words(B.words);
   words.resize(B.words.size() + B.fri_words, 0xdeadbeefu);
   std::vector<E4> ro(B.ro_count);
@@ -109,25 +125,27 @@ void run_host(const BSystem& sys, BVBatch& B, std::vector<u32>& fail) {
   for (size_t t = 0; t < B.items.size(); t++) bbv_path_body(d, (u32)t);
 }
 
-// verify_batch for a batch of `copies` of one proof, with run_host in the place of bvbatch_run
+// verify_batch_run for a batch of `copies` of one proof, with run_host in the place of vbatch_run
 int batch_verdict(const BSystem& sys, size_t n_claims, const u64* offs, const u32* data, const std::vector<uint8_t>& proof, int copies) {
   BVBatch B;
   std::vector<std::pair<size_t, int>> waiting;
   std::vector<int> verdicts(copies, -1);
   for (int i = 0; i < copies; i++) {
-    Prepared P(&sys.perm);
+    Prepared P(sys);
     const int v = verify_prepare(sys, n_claims, offs, data, proof.data(), proof.size(), P);
     if (v != V_OK) {
       verdicts[i] = v;
       continue;
     }
-    const int c = pcs_collect(sys, P.rounds, P.proof, P.ch, B, (u32)waiting.size());
-    if (c == COLLECT_HOST) {
+    const Challenger at_pcs = P.ch;
+    const int c = msamd::pcs_collect<BbVerify>(sys.params, P.rounds, P.proof, P.ch, B, (u32)waiting.size());
+    if (c == msamd::COLLECT_HOST) {
       g_host++;
-      verdicts[i] = -2;
+      Challenger ch = at_pcs;
+      verdicts[i] = pcs_verify(sys, P.rounds, P.proof, ch) ? verify_ood(sys, P) : V_INVALID_OPENING;
       continue;
     }
-    if (c == COLLECT_REFUSED) {
+    if (c == msamd::COLLECT_REFUSED) {
       g_refused++;
       verdicts[i] = V_INVALID_OPENING;
       continue;
@@ -154,11 +172,12 @@ int main(int argc, char** argv) {
   using namespace msbb;
   const std::string dir = argc > 1 ? argv[1] : ".";
   const int muts = argc > 2 ? atoi(argv[2]) : 200;
-  const char* names[] = {"arity1", "arity2", "arity3", "arity6", "caps_final", "evenodd", "evenodd_dead", "height1", "squares_mixed"};
+  const char* names[] = {"arity1", "arity2",  "arity3",       "arity6", "caps_final", "evenodd", "evenodd_dead", "evenodd_dead_table",
+                         "height1", "squares_mixed"};
   std::mt19937_64 rng(12345);
   size_t total = 0, disagree = 0, rejected = 0;
   {  // the sponge in a thread against hash_words, every length 0 .. 40, under three permutations
-    auto sys = host_system(slurp(dir + "/arity1.blob"));
+    auto sys = host_system(slurp(dir + "/arity1.blob"), {});
     for (u32 n = 0; n <= 40; n++) {
       std::vector<u32> v(n);
       for (auto& x : v) x = (u32)(rng() % BB_P);
@@ -173,7 +192,7 @@ int main(int argc, char** argv) {
     printf("sponge: 0..40 words agree with hash_words\n");
   }
   for (const char* nm : names) {
-    auto sys = host_system(slurp(dir + "/" + nm + ".blob"));
+    auto sys = host_system(slurp(dir + "/" + nm + ".blob"), slurp(dir + "/" + nm + ".precommit"));
     const auto cl = slurp(dir + "/" + std::string(nm) + ".claims");
     const auto proof = slurp(dir + "/" + std::string(nm) + ".proof");
     u64 n_claims;
@@ -186,6 +205,16 @@ int main(int argc, char** argv) {
     const int b = batch_verdict(*sys, n_claims, offs.data(), data.data(), proof, 3);
     printf("%-14s valid: verify %d, batch %d\n", nm, a, b);
     if (a != 0 || b != 0) return 1;
+    if (std::ifstream(dir + "/" + nm + ".width.proof").good()) {
+      // the directed mutation: a matrix opened at no point shows a longer row in the second query only. The collector cannot
+      // lay that out (COLLECT_HOST) and the batch must say what verify() says, between untouched copies or alone
+      const auto wide = slurp(dir + "/" + std::string(nm) + ".width.proof");
+      const size_t host_before = g_host;
+      const int wa = verify(*sys, n_claims, offs.data(), data.data(), wide.data(), wide.size());
+      const int wb = batch_verdict(*sys, n_claims, offs.data(), data.data(), wide, 3);
+      printf("%-14s row width differs between queries: verify %d, batch %d, host path taken %zu times\n", nm, wa, wb, g_host - host_before);
+      if (wa != wb || g_host - host_before != 3) return 1;
+    }
     size_t rej = 0, dis = 0;
     for (int k = 0; k < muts; k++) {
       std::vector<uint8_t> bad = proof;
