@@ -39,6 +39,8 @@ pub const MS_VERDICT_UNBALANCED: i32 = 6;
 pub const MS_CHECK_CONSTRAINT: u32 = 0x1;
 pub const MS_CHECK_LOOKUPS: u32 = 0x2;
 pub const MS_CHECK_CIRCUIT_WORDS: usize = 10;
+/// msbb_witness_check: the same mask; four accumulator coordinates per circuit
+pub const MSBB_CHECK_CIRCUIT_WORDS: usize = 12;
 
 /// One stage-1 trace in device memory (ms_witness_create_device / msbb_witness_create_device): element (r, c) is the unsigned
 /// little-endian integer of `elem_bytes` bytes at `ptr + (r * row_stride + c * col_stride) * elem_bytes`.
@@ -216,6 +218,9 @@ extern "C" {
     pub fn msbb_witness_create_device(sys: *mut msbb_system, traces: *const ms_dev_matrix, n_claims: usize, claim_offsets: *const u64,
                                       claim_data: *const u32, producer_stream: *mut c_void, out: *mut *mut msbb_witness) -> i32;
     pub fn msbb_witness_destroy(w: *mut msbb_witness);
+    pub fn msbb_witness_check(w: *mut msbb_witness, beta: *const u32, gamma: *const u32, verdict: *mut u32, circuits: *mut u64,
+                              root_counts: *mut u64, root_first: *mut u64, roots_cap: usize) -> i32;
+    pub fn msbb_system_check_info(sys: *const msbb_system, circuit: usize, out4: *mut u64) -> i32;
     pub fn msbb_prove(sys: *mut msbb_system, w: *mut msbb_witness, proof_out: *mut u8, cap: usize, proof_len: *mut usize,
                       stage_ms: *mut f64) -> i32;
     pub fn msbb_verify(sys: *mut msbb_system, n_claims: usize, claim_offsets: *const u64, claim_data: *const u32, proof: *const u8,

@@ -205,7 +205,7 @@ void ms_witness_destroy(ms_witness* w);
 
 /* ---- Witness check (what Plonky3 users know as check_constraints), on the device: does this witness satisfy the system, and
  * if not, WHERE not - for the price of one pass over the traces and one stage-2 build instead of a proof (no LDE, no tree, no
- * FRI). Goldilocks / BLAKE3 configuration only; a BabyBear counterpart (msbb_witness_check) does not exist yet.
+ * FRI). Goldilocks / BLAKE3 configuration; the BabyBear counterpart is msbb_witness_check (include/mstark_bb.h).
  *   Definition. For every active circuit (height n > 0) and every row r in [0, n) the circuit's user constraint roots (the
  * `zeros` of its compiled node program, in that order, index k) are evaluated on exactly the values the quotient kernels see on
  * the trace domain at x = w^r, w = the generator of the subgroup of order n: main and preprocessed variables at row r and, for

@@ -65,6 +65,36 @@ int32_t msbb_witness_create_device(msbb_system* sys, const ms_dev_matrix* traces
                                    msbb_witness** out);
 void msbb_witness_destroy(msbb_witness* w);
 
+/* ---- Witness check: ms_witness_check (include/mstark.h, "Witness check") for this configuration - its definition read over
+ * BabyBear. Every active circuit, every row r, the circuit's user constraint roots (`zeros`, in that order) on the values the
+ * BabyBear quotient kernel would see on the trace domain at x = w^r, w = the two-adic generator of order n (0x1a427a41 squared
+ * 27 - log n times): main and preprocessed variables at row r and (r + 1) mod n; is_first = n at row 0 (else 0), is_last = n w
+ * at row n - 1 (else 0), is_transition = w^r - w^-1; the stage-2 columns msbb_stage2_build makes under the caller's (beta,
+ * gamma) - four base coordinates per lookup - and the 16 public coordinates [beta, gamma, acc_in, acc_out], the accumulator
+ * chained as msbb_stage2_build chains it: the claims' accumulator first, then each active circuit's total. logUp constraints are
+ * not evaluated; of the lookups the balance is checked: the accumulator behind the last active circuit must be zero in all four
+ * coordinates.
+ *   Report. *verdict: the mask of MS_CHECK_CONSTRAINT | MS_CHECK_LOOKUPS. circuits: MSBB_CHECK_CIRCUIT_WORDS words per circuit
+ * of the system, inactive ones included:
+ *   [0] height  [1] failing rows  [2] smallest failing row  [3] smallest failing root at that row  [4] its value (canonical)
+ *   [5..8] the accumulator behind the circuit (canonical; zeros for an inactive circuit)  [9] number of roots  [10] which kernel
+ *   form ran (low byte: 1 thread per row / slots in LDS, 2 wave per row, 3 few lanes with large LDS, 4 global scratch, 0 none)
+ *   and its lanes per workgroup << 8  [11] where this circuit's roots start in root_counts / root_first.
+ * [2], [3] are all-ones when no row fails. root_counts / root_first: as for ms_witness_check; MS_ERR_BUFFER when roots_cap is
+ * below the system's total. Every figure is deterministic. A failed check is MS_OK with a non-zero verdict.
+ *   Misuse (MS_ERR, text via ms_last_error(), the context stays usable): a host-resident witness (msbb_witness_create_host); a
+ * coordinate of beta or gamma >= p; a null argument. Accepted: msbb_witness_create, msbb_witness_create_device. The witness is
+ * not changed: msbb_prove behind a check writes the bytes it writes without one. Host waits: one per call, for the report
+ * (the first check of a circuit also builds its check program). */
+#define MSBB_CHECK_CIRCUIT_WORDS 12
+int32_t msbb_witness_check(msbb_witness* w, const uint32_t beta[4], const uint32_t gamma[4], uint32_t* verdict,
+                           uint64_t* circuits /* n_circuits x MSBB_CHECK_CIRCUIT_WORDS */, uint64_t* root_counts /* nullable */,
+                           uint64_t* root_first /* nullable */, size_t roots_cap);
+/* out4 = [user constraint roots = constraint_count - 4 max(num_lookups, 1), live slots of the check's program, steps of its
+ * wave-per-row schedule (0: none), lanes per workgroup of the thread-per-row form with 4-byte slots in LDS: 256 up to 63 slots,
+ * 128 up to 127, 64 up to 255 (0: the slot file does not fit)] */
+int32_t msbb_system_check_info(const msbb_system* sys, size_t circuit, uint64_t out4[4]);
+
 /* Writes Proof::to_bytes (src/prover.rs:241-248). stage_ms (optional, 6 doubles) as for ms_prove. */
 int32_t msbb_prove(msbb_system* sys, msbb_witness* w, uint8_t* proof_out, size_t cap, size_t* proof_len, double* stage_ms);
 

@@ -525,16 +525,17 @@ _NONE = (1 << 64) - 1
 
 
 class CircuitCheck:
-    """One circuit's part of a CheckReport (the ten words of ms_witness_check, named)."""
+    """One circuit's part of a CheckReport (the ten words of ms_witness_check, named; with ext_d = 4 the twelve words of
+    msbb_witness_check, whose accumulator has four coordinates)."""
 
-    def __init__(self, index, words, root_counts, root_first, name=None, origins=None):
+    def __init__(self, index, words, root_counts, root_first, name=None, origins=None, ext_d=2):
         self.index, self.name, self.origins = index, name, origins
         self.height, self.failing_rows = int(words[0]), int(words[1])
         # (row, constraint root index, value) of the smallest failing row and the smallest failing root there; None = clean
         self.first_failure = None if int(words[2]) == _NONE else (int(words[2]), int(words[3]), int(words[4]))
-        self.accumulator = (int(words[5]), int(words[6]))
-        self.roots = int(words[7])
-        self.kernel, self.lanes = int(words[8]) & 0xFF, int(words[8]) >> 8
+        self.accumulator = tuple(int(x) for x in words[5:5 + ext_d])
+        self.roots = int(words[5 + ext_d])
+        self.kernel, self.lanes = int(words[6 + ext_d]) & 0xFF, int(words[6 + ext_d]) >> 8
         self.root_counts = root_counts  # np.uint64 per root: rows where it is non-zero
         self.root_first = root_first    # np.uint64 per root: the first such row (all-ones: none)
 
@@ -565,17 +566,17 @@ class CircuitCheck:
 class CheckReport:
     """What SystemWitness.check returns: .verdict (mask of CHECK_CONSTRAINT / CHECK_LOOKUPS), .ok, .circuits[i]"""
 
-    def __init__(self, verdict, circuits, beta, gamma):
+    def __init__(self, verdict, circuits, beta, gamma, ext_d=2):
         self.verdict, self.circuits, self.beta, self.gamma = verdict, circuits, beta, gamma
         self.ok = verdict == 0
-        self.final_accumulator = next((c.accumulator for c in reversed(circuits) if c.height), (0, 0))
+        self.final_accumulator = next((c.accumulator for c in reversed(circuits) if c.height), (0,) * ext_d)
 
     def __str__(self):
         if self.ok:
             return "witness satisfies the system (%d active circuits)" % sum(1 for c in self.circuits if c.height)
         out = [ln for c in self.circuits for ln in c.lines()]
         if self.verdict & CHECK_LOOKUPS:
-            out.append("lookups unbalanced: the accumulator ends at (0x%016x, 0x%016x)" % self.final_accumulator)
+            out.append("lookups unbalanced: the accumulator ends at (%s)" % ", ".join("0x%016x" % x for x in self.final_accumulator))
         return "\n".join(out)
 
 

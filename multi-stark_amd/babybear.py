@@ -23,7 +23,7 @@ def exported_symbols():
             "msbb_challenger_create", "msbb_challenger_destroy", "msbb_challenger_observe", "msbb_challenger_observe_digests",
             "msbb_challenger_sample_ext", "msbb_challenger_sample_bits", "msbb_challenger_observe_claims", "msbb_trace_destroy", "msbb_trace_info",
             "msbb_system_preprocessed_mmcs", "msbb_witness_commit_stage1", "msbb_witness_claims_accumulator", "msbb_stage2_build",
-            "msbb_pcs_commit_traces", "msbb_quotient", "msbb_pcs_commit_ldes", "msbb_pcs_open"]
+            "msbb_pcs_commit_traces", "msbb_quotient", "msbb_pcs_commit_ldes", "msbb_pcs_open", "msbb_witness_check", "msbb_system_check_info"]
 
 
 import sys
@@ -63,7 +63,42 @@ class Proof:
         return self._data
 
 
+# Witness.check: the challenges used when the caller gives none - fixed, non-trivial (the first hexadecimal digits of pi, 32 bits
+# at a time, reduced mod p), so that a report is reproducible. They are public: a witness made to balance under exactly these
+# passes the lookup part of the check; a caller who fears that passes its own.
+CHECK_BETA = tuple(x % P for x in (0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344))
+CHECK_GAMMA = tuple(x % P for x in (0xA4093822, 0x299F31D0, 0x082EFA98, 0xEC4E6C89))
+CHECK_CIRCUIT_WORDS = 12  # MSBB_CHECK_CIRCUIT_WORDS of include/mstark_bb.h
+
+
 class Witness:
+    def check(self, beta=None, gamma=None, names=None, origins=None):
+        """msbb_witness_check: every user constraint root of every active circuit on the trace domain, and the lookup balance
+        under (beta, gamma) - four canonical coordinates each, default CHECK_BETA / CHECK_GAMMA. -> the package's CheckReport
+        with four-coordinate accumulators. names / origins (optional, per circuit): labels and CompiledCircuit.zero_origins for
+        the text of the report."""
+        pkg = _pkg()
+        beta = CHECK_BETA if beta is None else tuple(int(x) for x in beta)
+        gamma = CHECK_GAMMA if gamma is None else tuple(int(x) for x in gamma)
+        sysm = self.system
+        nc = sysm.n_circuits
+        roots = [sysm.check_info(i)["roots"] for i in range(nc)]
+        total = sum(roots)
+        words = np.zeros((max(nc, 1), CHECK_CIRCUIT_WORDS), dtype=np.uint64)
+        cnt, first = np.zeros(max(total, 1), dtype=np.uint64), np.zeros(max(total, 1), dtype=np.uint64)
+        verdict = C.c_uint32()
+        b, g = _raw32(beta), _raw32(gamma)  # (a coordinate >= p is the entry point's to refuse)
+        if b.size != 4 or g.size != 4:
+            raise pkg.MstarkError("beta and gamma have four coordinates each")
+        _check(_lib().msbb_witness_check(self.h, _p32(b), _p32(g), C.byref(verdict), words.ctypes.data_as(u64p), cnt.ctypes.data_as(u64p),
+                                         first.ctypes.data_as(u64p), C.c_size_t(total)))
+        circuits = []
+        for i in range(nc):
+            o = int(words[i, 11])
+            circuits.append(pkg.CircuitCheck(i, words[i], cnt[o:o + roots[i]].copy(), first[o:o + roots[i]].copy(),
+                                             names[i] if names else None, origins[i] if origins else None, ext_d=4))
+        return pkg.CheckReport(int(verdict.value), circuits, beta, gamma, ext_d=4)
+
     def __init__(self, system, traces, claims_packed, host_resident=False):
         """host_resident: the witness stays in host memory (msbb_witness_create_host) and every proof uploads it - the
         reference's timed region; the arrays are kept alive (and page-locked) by this object"""
@@ -118,6 +153,12 @@ class System:
         keys = ["main_width", "pre_width", "pre_height", "num_lookups", "stage2_width", "constraint_count", "max_constraint_degree",
                 "quotient_degree", "args_width"]
         return dict(zip(keys, (int(x) for x in o)))
+
+    def check_info(self, ci):
+        """msbb_system_check_info: what the witness check adds to circuit_info"""
+        o = np.zeros(4, dtype=np.uint64)
+        _check(_lib().msbb_system_check_info(self.h, C.c_size_t(ci), o.ctypes.data_as(u64p)))
+        return dict(zip(["roots", "slots", "wave_steps", "lds_lanes"], (int(x) for x in o)))
 
     def circuit_kernels(self, ci):
         """msbb_system_circuit_kernels: KERNEL_QUOTIENT when the circuit's quotient kernel was generated and compiled, else 0"""

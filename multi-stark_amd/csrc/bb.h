@@ -41,6 +41,20 @@ struct BPcsData {
   BTree tree;
 };
 
+// HIP-event timing of one launch for a kernel class (ms_ctx_set_profile_mask): the classes are those of the Goldilocks
+// path; `units` counts Poseidon2 permutations for the hash classes (bench.py prices them against the VALU issue peak)
+struct ProfScope {
+  Ctx& ctx;
+  int id;
+  hipEvent_t ev;
+  double bytes, units;
+  ProfScope(Ctx& c, int kid, double alg_bytes, double n_units = 0) : ctx(c), id(kid), ev(c.prof_begin(kid)), bytes(alg_bytes), units(n_units) {}
+  ~ProfScope() {
+    if (ev) ctx.stats[id].units += units;
+    ctx.prof_end(id, ev, bytes);
+  }
+};
+
 // ---- layout / conversion
 void bb_upload_rows(Ctx& ctx, const u32* host_rowmajor_canonical, size_t h, size_t w, BMat& out);
 void bb_upload_rows_async(Ctx& ctx, const u32* host_rowmajor_canonical, size_t h, size_t w, BMat& out);  // queued, no synchronisation
@@ -83,8 +97,13 @@ struct BLookupsDev {
 // circuit's local total (added to the running accumulator by the caller)
 void bb_stage2(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookupsDev& lk, const BMat& trace, const BMat* pre, E4 beta,
                E4 gamma, BMat& out, E4* total);
+// the same launches without the read-back: the total stays in device memory (d_total; nullable for a circuit without lookups,
+// whose total is zero). bb_stage2 is this plus the read-back.
+void bb_stage2_async(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookupsDev& lk, const BMat& trace, const BMat* pre, E4 beta,
+                     E4 gamma, BMat& out, E4* d_total);
 // sum over the claims of 1 / (beta + fingerprint(gamma, claim)) (src/prover.rs:382-387); data in Montgomery form
 E4 bb_claims_accumulator(Ctx& ctx, const u32* d_data_monty, const u64* d_offs, size_t n, E4 beta, E4 gamma);
+void bb_claims_accumulator_async(Ctx& ctx, const u32* d_data_monty, const u64* d_offs, size_t n, E4 beta, E4 gamma, E4* d_total);  // no read-back
 // proof-of-work search of the duplex challenger on the device: smallest canonical witness
 u32 bb_grind(Ctx& ctx, const Poseidon2* d_perm, const u32* state16, const u32* pending, unsigned n_pending, unsigned bits);
 // quotient_values (src/prover.rs:756-962) on the quotient domain; q_evals: (n q) x 4 in natural order

@@ -85,6 +85,14 @@ struct Challenger {
 struct Params {
   u64 log_blowup = 1, cap_height = 0, log_final_poly_len = 0, max_log_arity = 1, num_queries = 1, commit_pow_bits = 0, query_pow_bits = 0;
 };
+// the witness check's program of one circuit (bb_check.hip): the node vector lowered by msamd::build_program over the user
+// constraint roots alone - slot-allocated code, wave schedule - with the constants as Montgomery words in build_program's order.
+// Built on the first msbb_witness_check / msbb_system_check_info of the circuit; system creation and the prover never touch it.
+struct BCheckProgram {
+  bool built = false;
+  msamd::DProgram prog;
+  DBuf<u32> consts;
+};
 struct BCircuit {
   std::vector<PNode> nodes;
   std::vector<uint32_t> degrees, zeros;
@@ -96,6 +104,7 @@ struct BCircuit {
   BLookupsDev lk;
   DBuf<u32> d_zeros;
   BMat pre;  // preprocessed trace (column-major, Montgomery), for witness preparation
+  BCheckProgram check;
   size_t quotient_degree() const {
     size_t d = (max_constraint_degree > 2 ? max_constraint_degree : 2) - 1, q = 1;
     while (q < d) q <<= 1;
@@ -168,6 +177,12 @@ int verify(BSystem& sys, size_t n_claims, const u64* claim_offsets, const u32* c
 // bb_verify_dev.hip): verdicts[i] is what verify() returns for proof i
 void verify_batch(BSystem& sys, size_t n_proofs, const u64* n_claims, const u64* const* claim_offsets, const u32* const* claim_data,
                   const uint8_t* const* proofs, const u64* proof_lens, int32_t* verdicts);
+// msbb_witness_check (bb_check.hip): the user constraint roots of every active circuit on the trace domain + the lookup balance
+// under (beta, gamma); circuits: n_circuits x MSBB_CHECK_CIRCUIT_WORDS; root_counts / root_first nullable
+void witness_check(BSystem& sys, BWitness& wit, E4 beta, E4 gamma, uint32_t* verdict, u64* circuits, u64* root_counts, u64* root_first);
+size_t check_roots(const BCircuit& c);                        // user constraint roots (throws if `zeros` disagrees)
+const BCheckProgram& check_program(BSystem& sys, size_t ci);  // built on first use
+unsigned check_lds_lanes(size_t n_slots);                     // lanes of the thread-per-row LDS form (0: the slot file does not fit)
 // MerkleTreeMmcs::verify_batch for many openings of one commitment, one device thread per opening; everything canonical
 void mmcs_verify_batch_device(Ctx& ctx, const Poseidon2* d_perm, const std::vector<size_t>& heights, const std::vector<size_t>& widths,
                               const u32* cap, unsigned cap_height, size_t n_openings, const u64* indices, const u32* vals, const u32* siblings,

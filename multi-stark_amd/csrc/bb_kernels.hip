@@ -13,19 +13,6 @@ namespace msbb {
 using msamd::PNode;
 
 static inline unsigned blocks_for(size_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }
-// HIP-event timing of one launch for a kernel class (ms_ctx_set_profile_mask): the classes are those of the Goldilocks
-// path; `units` counts Poseidon2 permutations for the hash classes (bench.py prices them against the VALU issue peak)
-struct ProfScope {
-  Ctx& ctx;
-  int id;
-  hipEvent_t ev;
-  double bytes, units;
-  ProfScope(Ctx& c, int kid, double alg_bytes, double n_units = 0) : ctx(c), id(kid), ev(c.prof_begin(kid)), bytes(alg_bytes), units(n_units) {}
-  ~ProfScope() {
-    if (ev) ctx.stats[id].units += units;
-    ctx.prof_end(id, ev, bytes);
-  }
-};
 
 __device__ __forceinline__ size_t bitrev_dev(size_t x, unsigned bits) { return bits ? (size_t)(__brevll((unsigned long long)x) >> (64 - bits)) : 0; }
 
@@ -761,19 +748,19 @@ __global__ void stage2_write_k(const E4* __restrict__ v, const E4* __restrict__ 
 #pragma unroll
   for (int k = 0; k < 4; k++) out[(4 * l + k) * ld + r] = x.c[k];
 }
-void bb_stage2(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookupsDev& lk, const BMat& trace, const BMat* pre, E4 beta, E4 gamma,
-               BMat& out, E4* total) {
+void bb_stage2_async(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookupsDev& lk, const BMat& trace, const BMat* pre, E4 beta,
+                     E4 gamma, BMat& out, E4* d_total) {
   size_t n = trace.h, L = lk.L;
   out = bmat(ctx, n, 4 * std::max<size_t>(L, 1));
-  *total = e4_zero();
   if (L == 0) {  // pass-through accumulator column: zeros (src/lookup.rs:520-523)
     HIP_CHECK(hipMemsetAsync(out.buf.p, 0, n * 4 * 4, ctx.stream));
+    if (d_total) HIP_CHECK(hipMemsetAsync(d_total, 0, sizeof(E4), ctx.stream));
     return;
   }
   DBuf<u32> scratch(ctx, std::max<size_t>(prefix_len, 1) * n);
   DBuf<E4> terms(ctx, n * L);
   size_t nb = (n * L + 1023) / 1024;
-  DBuf<E4> tot(ctx, nb + 1);
+  DBuf<E4> tot(ctx, nb);  // (released behind the launches below: the pool hands a block on in stream order)
   Stage2Args a;
   a.kind = prog.kind.p, a.na = prog.a.p, a.nb = prog.b.p, a.prefix_len = (unsigned)prefix_len;
   a.lk_mult = lk.mult.p, a.lk_off = lk.arg_off.p, a.lk_args = lk.args.p, a.L = (unsigned)L;
@@ -782,9 +769,19 @@ void bb_stage2(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookups
   a.n = n, a.beta = beta, a.gamma = gamma, a.scratch = scratch.p, a.terms = terms.p;
   stage2_terms_k<<<blocks_for(n, 256), 256, 0, ctx.stream>>>(a);
   scan_local_k<<<(unsigned)nb, 256, 0, ctx.stream>>>(terms.p, n * L, tot.p);
-  scan_totals_k<<<1, 1024, 0, ctx.stream>>>(tot.p, nb, tot.p + nb);
+  scan_totals_k<<<1, 1024, 0, ctx.stream>>>(tot.p, nb, d_total);
   stage2_write_k<<<blocks_for(n * L, 256), 256, 0, ctx.stream>>>(terms.p, tot.p, n, (unsigned)L, out.buf.p, out.ld);
-  ctx.d2h(total, tot.p + nb, sizeof(E4));
+}
+void bb_stage2(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookupsDev& lk, const BMat& trace, const BMat* pre, E4 beta, E4 gamma,
+               BMat& out, E4* total) {
+  *total = e4_zero();
+  if (lk.L == 0) {  // no total to read back: no launch for it, no host wait
+    bb_stage2_async(ctx, prog, prefix_len, lk, trace, pre, beta, gamma, out, nullptr);
+    return;
+  }
+  DBuf<E4> d_total(ctx, 1);
+  bb_stage2_async(ctx, prog, prefix_len, lk, trace, pre, beta, gamma, out, d_total.p);
+  ctx.d2h(total, d_total.p, sizeof(E4));
 }
 
 // claims accumulator (src/prover.rs:382-387): sum over the claims of 1 / (beta + fingerprint(gamma, claim))
@@ -798,16 +795,24 @@ __global__ void claims_terms_k(const u32* __restrict__ data, const u64* __restri
   }
   terms[i] = e4_inv(e4_add(beta, f));
 }
-E4 bb_claims_accumulator(Ctx& ctx, const u32* d_data_monty, const u64* d_offs, size_t n, E4 beta, E4 gamma) {
-  if (!n) return e4_zero();
+void bb_claims_accumulator_async(Ctx& ctx, const u32* d_data_monty, const u64* d_offs, size_t n, E4 beta, E4 gamma, E4* d_total) {
+  if (!n) {
+    HIP_CHECK(hipMemsetAsync(d_total, 0, sizeof(E4), ctx.stream));
+    return;
+  }
   DBuf<E4> terms(ctx, n);
   size_t nb = (n + 1023) / 1024;
-  DBuf<E4> tot(ctx, nb + 1);
+  DBuf<E4> tot(ctx, nb);
   claims_terms_k<<<blocks_for(n, 256), 256, 0, ctx.stream>>>(d_data_monty, d_offs, n, beta, gamma, terms.p);
   scan_local_k<<<(unsigned)nb, 256, 0, ctx.stream>>>(terms.p, n, tot.p);
-  scan_totals_k<<<1, 1024, 0, ctx.stream>>>(tot.p, nb, tot.p + nb);
+  scan_totals_k<<<1, 1024, 0, ctx.stream>>>(tot.p, nb, d_total);
+}
+E4 bb_claims_accumulator(Ctx& ctx, const u32* d_data_monty, const u64* d_offs, size_t n, E4 beta, E4 gamma) {
+  if (!n) return e4_zero();
+  DBuf<E4> d_total(ctx, 1);
+  bb_claims_accumulator_async(ctx, d_data_monty, d_offs, n, beta, gamma, d_total.p);
   E4 total;
-  ctx.d2h(&total, tot.p + nb, sizeof(E4));
+  ctx.d2h(&total, d_total.p, sizeof(E4));
   return total;
 }
 

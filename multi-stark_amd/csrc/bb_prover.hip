@@ -1514,6 +1514,37 @@ int32_t msbb_stage2_build(msbb_witness* w, const uint32_t beta[4], const uint32_
   return MS_OK;
   BB_CATCH
 }
+int32_t msbb_witness_check(msbb_witness* w, const uint32_t beta[4], const uint32_t gamma[4], uint32_t* verdict, uint64_t* circuits,
+                           uint64_t* root_counts, uint64_t* root_first, size_t roots_cap) {
+  BB_TRY
+  if (!w || !beta || !gamma || !verdict || !circuits) throw std::runtime_error("msbb_witness_check: null argument");
+  BWitness& wit = *w->w;
+  BSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  const E4 b = e4_in(beta), g = e4_in(gamma);
+  if (root_counts || root_first) {
+    size_t total = 0;
+    for (auto& c : sys.circuits) total += check_roots(c);
+    if (roots_cap < total) return MS_ERR_BUFFER;
+  }
+  witness_check(sys, wit, b, g, verdict, circuits, root_counts, root_first);
+  return MS_OK;
+  BB_CATCH
+}
+int32_t msbb_system_check_info(const msbb_system* sys, size_t circuit, uint64_t out4[4]) {
+  BB_TRY
+  if (!sys || !out4) throw std::runtime_error("msbb_system_check_info: null argument");
+  BSystem& s = *sys->sys;
+  if (circuit >= s.circuits.size()) throw std::runtime_error("circuit index out of range");
+  HIP_CHECK(hipSetDevice(s.ctx->device));
+  out4[0] = check_roots(s.circuits[circuit]);
+  const BCheckProgram& cp = check_program(s, circuit);  // built here if no check has run yet
+  out4[1] = cp.prog.n_slots;
+  out4[2] = cp.prog.wave_steps;
+  out4[3] = check_lds_lanes(cp.prog.n_slots);
+  return MS_OK;
+  BB_CATCH
+}
 static int32_t commit_handles(msbb_system* sys, size_t n, msbb_trace* const* ts, int kind, uint32_t* cap_out, msbb_mmcs** out) {
   BB_TRY
   if (!sys || !n || !ts || !cap_out || !out) throw std::runtime_error("null argument");
