@@ -39,6 +39,9 @@ pub const MS_VERDICT_UNBALANCED: i32 = 6;
 pub const MS_CHECK_CONSTRAINT: u32 = 0x1;
 pub const MS_CHECK_LOOKUPS: u32 = 0x2;
 pub const MS_CHECK_CIRCUIT_WORDS: usize = 10;
+/// ms_witness_lookup_balance: words per entry; the circuit word of an entry whose first origin is a claim
+pub const MS_LB_ENTRY_WORDS: usize = 8;
+pub const MS_LB_CLAIMS: u64 = !0;
 /// msbb_witness_check: the same mask; four accumulator coordinates per circuit
 pub const MSBB_CHECK_CIRCUIT_WORDS: usize = 12;
 
@@ -187,6 +190,8 @@ extern "C" {
     pub fn ms_witness_check(w: *mut ms_witness, beta: *const u64, gamma: *const u64, verdict: *mut u32, circuits: *mut u64,
                             root_counts: *mut u64, root_first: *mut u64, roots_cap: usize) -> i32;
     pub fn ms_system_check_info(sys: *const ms_system, circuit: usize, out4: *mut u64) -> i32;
+    pub fn ms_witness_lookup_balance(w: *mut ms_witness, summary: *mut u64, entries: *mut u64, entries_cap: usize, args_out: *mut u64,
+                                     args_cap: usize, slot_counts: *mut u64, slots_cap: usize) -> i32;
     pub fn ms_witness_claims_accumulator(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_out: *mut u64) -> i32;
     pub fn ms_stage2_build(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_in: *const u64, accs_out: *mut u64,
                            traces_out: *mut *mut ms_trace) -> i32;

@@ -245,6 +245,45 @@ int32_t ms_witness_check(ms_witness* w, const uint64_t beta[2], const uint64_t g
  * (0: none), lanes per workgroup of the check's thread-per-row form with slots in LDS (0: the slot file does not fit)] */
 int32_t ms_system_check_info(const ms_system* sys, size_t circuit, uint64_t out4[4]);
 
+/* ---- Lookup balance, exact, on the device: WHICH messages do not cancel. ms_witness_check says of the lookups one bit
+ * (MS_CHECK_LOOKUPS); this call groups every message of the witness by its tuple and names the groups whose multiplicities do
+ * not sum to zero, with where they came from. It takes no challenges. Goldilocks / BLAKE3 configuration.
+ *   Definition. A message is (a) a claim i: tuple claim_data[off[i] .. off[i + 1]), multiplicity 1 (src/prover.rs:382-387), or
+ * (b) a triple (active circuit c, row r, lookup slot j) with the multiplicity and arguments of SystemWitness::from_stage_1
+ * (src/system.rs:244-328, src/lookup.rs:392-405). A message of multiplicity 0 (padding rows) does not exist for this check. Two
+ * messages belong to the same GROUP when their tuples are equal after trailing zeros are stripped: the fingerprint is a Horner
+ * evaluation (src/lookup.rs:373-384,410-414), so (a, b, 0) and (a, b) are one message to the protocol, and so are the empty
+ * tuple and (0, 0). A group's NET is the sum of its multiplicities modulo p; a group is UNBALANCED when its net is not 0.
+ * Messages are ordered by ORIGIN: claims first, by index; then the circuits in system order, row-major, slot last. A group's
+ * FIRST ORIGIN is the smallest origin among its members. The witness is balanced exactly when no group is unbalanced. Balance
+ * implies that ms_witness_check reports no MS_CHECK_LOOKUPS under every (beta, gamma) whose messages are invertible; imbalance
+ * implies the bit, except with the probability the proof system itself accepts.
+ *   Report. summary: [0] messages of non-zero multiplicity  [1] groups  [2] unbalanced groups  [3] entries written =
+ * min([2], entries_cap). entries (entries_cap x MS_LB_ENTRY_WORDS words; nullable with entries_cap 0): the unbalanced groups with
+ * the smallest first origins, in ascending order of first origin, whatever their total number:
+ *   [0] circuit of the first origin (MS_LB_CLAIMS: a claim)  [1] its row (the claim's index)  [2] its lookup slot (0 for a claim)
+ *   [3] net, canonical, non-zero  [4] members  [5] length of the stripped tuple  [6] where the tuple starts in args_out; the
+ *   tuples are packed in entry order, and [6] is all-ones for a tuple that would end behind args_cap  [7] reserved, 0.
+ * args_out (args_cap words; nullable with args_cap 0): the stripped tuples. slot_counts (nullable, slots_cap words): one word per
+ * lookup slot of every circuit of the system in system order (inactive circuits: zeros), then one word for the claims - the
+ * number of messages from that source that belong to an unbalanced group; MS_ERR_BUFFER when slots_cap is below
+ * sum(num_lookups) + 1. Every figure is deterministic: nothing depends on the order in which threads ran, nor on the hash.
+ *   An unbalanced witness is MS_OK. MS_ERR (text via ms_last_error(), the context stays usable) is for misuse: a host-resident
+ * witness; a witness with circuits (or claims) held by another rank; a null w or summary; a null buffer with a non-zero capacity.
+ * A system without lookups and without claims: MS_OK, zeros. The witness is not changed: ms_prove behind the call writes the bytes
+ * it writes without it. A circuit whose lookup values the witness does not hold (ms_witness_create_device: its stage 2 reads the
+ * trace) has them computed into temporaries of the call; a lookup prefix that does not fit the device sweep is MS_ERR.
+ *   Memory: the grouping table takes 40 bytes x cap, cap = the power of two >= max(64, 2 x M), M = claims + sum over the active
+ * circuits of height x num_lookups (1.34 GB at 2^20 additions, M = 14 x 2^20), plus M / 8 bytes of marks; an allocation failure
+ * is MS_ERR naming the bytes. MSAMD_LB_HASH_BITS=k (diagnostics, read per call) keeps only the low k bits of the hash: with 0
+ * every probe sequence starts at slot 0 - the report is the same, by a longer way.
+ *   Host waits: one when the witness is balanced; one more, to fetch entries and tuples, when it is not and entries_cap > 0. */
+#define MS_LB_ENTRY_WORDS 8
+#define MS_LB_CLAIMS (~(uint64_t)0)
+int32_t ms_witness_lookup_balance(ms_witness* w, uint64_t summary[4], uint64_t* entries, size_t entries_cap /* nullable with cap 0 */,
+                                  uint64_t* args_out, size_t args_cap /* nullable with cap 0 */, uint64_t* slot_counts /* nullable */,
+                                  size_t slots_cap);
+
 /* ---- System::prove_multiple_claims (src/prover.rs:290-603). Writes Proof::to_bytes (src/prover.rs:241-248).
  * stage_ms (optional, 6 doubles): stage1_commit, lookup_construction, stage2_commit, quotient, fri_open, total —
  * the reference's span names (src/prover.rs:336-538). Returns MS_ERR_BUFFER with *proof_len = needed size if

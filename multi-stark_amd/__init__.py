@@ -52,7 +52,7 @@ def exported_symbols():
             "ms_challenger_sample_bits", "ms_stage2_trace", "ms_claims_accumulator",
             "ms_quotient_values", "ms_field_op", "ms_trace_destroy", "ms_trace_info", "ms_system_preprocessed_mmcs",
             "ms_witness_commit_stage1", "ms_challenger_observe_claims", "ms_witness_claims_accumulator", "ms_stage2_build",
-            "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes", "ms_witness_check", "ms_system_check_info"]
+            "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes", "ms_witness_check", "ms_system_check_info", "ms_witness_lookup_balance"]
 
 
 # ms_system_circuit_kernels / msbb_system_circuit_kernels (MS_KERNEL_* in include/mstark.h)
@@ -580,8 +580,89 @@ class CheckReport:
         return "\n".join(out)
 
 
+LB_ENTRY_WORDS = 8  # MS_LB_ENTRY_WORDS of include/mstark.h
+_P = (1 << 64) - (1 << 32) + 1
+
+
+class BalanceEntry:
+    """One unbalanced group of a LookupBalanceReport: .origin = (circuit or "claims", row or claim index, lookup slot) of its
+    first member, .net (canonical, non-zero), .members, .args (the tuple without trailing zeros; None: it did not fit)"""
+
+    def __init__(self, origin, net, members, args):
+        self.origin, self.net, self.members, self.args = origin, net, members, args
+
+    def fields(self):
+        return (self.origin, self.net, self.members, self.args)
+
+    def line(self, names=None):
+        c, r, j = self.origin
+        net = self.net - _P if self.net > _P // 2 else self.net
+        tup = "(?)" if self.args is None else "(%s)" % ", ".join(str(a) for a in self.args)
+        if c == "claims":
+            where = "claim %d" % r
+        else:
+            where = "circuit %d%s row %d lookup %d" % (c, " (%s)" % names[c] if names else "", r, j)
+        return "%s: net %d over %d message%s, first at %s" % (tup, net, self.members, "" if self.members == 1 else "s", where)
+
+
+class LookupBalanceReport:
+    """What SystemWitness.lookup_balance returns: .ok, .messages, .groups, .unbalanced, .entries (BalanceEntry, ascending first
+    origin, at most as many as asked for), .slot_counts[circuit][slot] and .claims_count (messages of unbalanced groups)"""
+
+    def __init__(self, messages, groups, unbalanced, entries, slot_counts, claims_count, names=None):
+        self.messages, self.groups, self.unbalanced, self.entries = messages, groups, unbalanced, entries
+        self.slot_counts, self.claims_count, self.names = slot_counts, claims_count, names
+        self.ok = unbalanced == 0
+
+    def fields(self):
+        """everything, as plain values (what a model of the call reproduces)"""
+        return (self.messages, self.groups, self.unbalanced, [e.fields() for e in self.entries], self.slot_counts, self.claims_count)
+
+    def __str__(self):
+        if self.ok:
+            return "lookups balanced (%d messages in %d groups)" % (self.messages, self.groups)
+        out = [e.line(self.names) for e in self.entries]
+        if self.unbalanced > len(self.entries):
+            out.append("... and %d more unbalanced groups (%d in all)" % (self.unbalanced - len(self.entries), self.unbalanced))
+        for c, counts in enumerate(self.slot_counts):
+            for j, n in enumerate(counts):
+                if n:
+                    out.append("circuit %d%s lookup %d: %d messages in unbalanced groups" % (c, " (%s)" % self.names[c] if self.names else "", j, n))
+        if self.claims_count:
+            out.append("claims: %d messages in unbalanced groups" % self.claims_count)
+        return "\n".join(out)
+
+
 class SystemWitness:
     """Device-resident SystemWitness + claims (ms_witness). Built by `System.witness`."""
+
+    def lookup_balance(self, entries=64, names=None):
+        """ms_witness_lookup_balance: every message of the witness grouped by its tuple, exactly (no challenges); the groups
+        whose multiplicities do not cancel, with where they came from. -> LookupBalanceReport with at most `entries` entries.
+        names (optional, per circuit): labels for the text of the report."""
+        sysm = self.system
+        nl = [sysm.circuit_info(i)["num_lookups"] for i in range(sysm.n_circuits)]
+        total = sum(nl)
+        summary, counts = np.zeros(4, dtype=np.uint64), np.zeros(total + 1, dtype=np.uint64)
+        ent = np.zeros((max(entries, 1), LB_ENTRY_WORDS), dtype=np.uint64)
+        args_cap = 64 * max(entries, 1)
+        while True:
+            args = np.zeros(args_cap, dtype=np.uint64)
+            _check(lib().ms_witness_lookup_balance(self.h, _p(summary), _p(ent), C.c_size_t(entries), _p(args), C.c_size_t(args_cap), _p(counts),
+                                                   C.c_size_t(total + 1)))
+            n = int(summary[3])
+            need = int(ent[:n, 5].sum())
+            if need <= args_cap:
+                break
+            args_cap = need  # some tuple did not fit: the lengths are known now
+        out = []
+        for e in ent[:n]:
+            origin = ("claims", int(e[1]), 0) if int(e[0]) == _NONE else (int(e[0]), int(e[1]), int(e[2]))
+            a = None if int(e[6]) == _NONE else [int(x) for x in args[int(e[6]):int(e[6]) + int(e[5])]]
+            out.append(BalanceEntry(origin, int(e[3]), int(e[4]), a))
+        offs = np.cumsum([0] + nl)
+        slot_counts = [[int(x) for x in counts[offs[i]:offs[i + 1]]] for i in range(sysm.n_circuits)]
+        return LookupBalanceReport(int(summary[0]), int(summary[1]), int(summary[2]), out, slot_counts, int(counts[total]), names)
 
     def check(self, beta=None, gamma=None, names=None, origins=None):
         """ms_witness_check: every user constraint root of every active circuit on the trace domain, and the lookup balance

@@ -373,6 +373,18 @@ int32_t ms_witness_check(ms_witness* w, const uint64_t beta[2], const uint64_t g
   return MS_OK;
   MS_CATCH
 }
+int32_t ms_witness_lookup_balance(ms_witness* w, uint64_t summary[4], uint64_t* entries, size_t entries_cap, uint64_t* args_out, size_t args_cap,
+                                  uint64_t* slot_counts, size_t slots_cap) {
+  MS_TRY if (!w || !summary) throw std::runtime_error("ms_witness_lookup_balance: null argument");
+  if ((!entries && entries_cap) || (!args_out && args_cap)) throw std::runtime_error("ms_witness_lookup_balance: null buffer with a non-zero capacity");
+  HWitness& wit = *w->w;
+  HSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  if (slot_counts && slots_cap < lookup_balance_slots(sys) + 1) return MS_ERR_BUFFER;
+  witness_lookup_balance(sys, wit, summary, entries, entries_cap, args_out, args_cap, slot_counts);
+  return MS_OK;
+  MS_CATCH
+}
 int32_t ms_system_check_info(const ms_system* sys, size_t ci, uint64_t out4[4]) {
   MS_TRY if (!sys || !out4) throw std::runtime_error("ms_system_check_info: null argument");
   const HSystem& s = *sys->sys;

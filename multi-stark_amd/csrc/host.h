@@ -222,6 +222,11 @@ void observe_claims(Ctx& ctx, Challenger& ch, HWitness& wit);
 void witness_check(HSystem& sys, HWitness& wit, E2 beta, E2 gamma, uint32_t* verdict, u64* circuits, u64* root_counts, u64* root_first);
 size_t check_roots(const HCircuit& c);          // constraint_count - 2 max(num_lookups, 1), checked against HCircuit::zeros
 unsigned check_lds_lanes(size_t n_slots);       // lanes per workgroup of the check's LDS tier (0: the slot file does not fit)
+// ms_witness_lookup_balance (balance.hip): the witness's messages grouped by tuple, exactly; slot_counts (nullable) has
+// lookup_balance_slots(sys) + 1 words. One host wait, a second one for the entries when some group is unbalanced
+void witness_lookup_balance(HSystem& sys, HWitness& wit, u64 summary[4], u64* entries, size_t entries_cap, u64* args_out, size_t args_cap,
+                            u64* slot_counts);
+size_t lookup_balance_slots(const HSystem& sys);  // sum of num_lookups over every circuit of the system
 void field_op(Ctx& ctx, int op, const u64* a, const u64* b, size_t n, u64* out);
 
 }  // namespace msamd
