@@ -226,6 +226,8 @@ extern "C" {
     pub fn msbb_witness_check(w: *mut msbb_witness, beta: *const u32, gamma: *const u32, verdict: *mut u32, circuits: *mut u64,
                               root_counts: *mut u64, root_first: *mut u64, roots_cap: usize) -> i32;
     pub fn msbb_system_check_info(sys: *const msbb_system, circuit: usize, out4: *mut u64) -> i32;
+    pub fn msbb_witness_lookup_balance(w: *mut msbb_witness, summary: *mut u64, entries: *mut u64, entries_cap: usize, args_out: *mut u32,
+                                       args_cap: usize, slot_counts: *mut u64, slots_cap: usize) -> i32;
     pub fn msbb_prove(sys: *mut msbb_system, w: *mut msbb_witness, proof_out: *mut u8, cap: usize, proof_len: *mut usize,
                       stage_ms: *mut f64) -> i32;
     pub fn msbb_verify(sys: *mut msbb_system, n_claims: usize, claim_offsets: *const u64, claim_data: *const u32, proof: *const u8,

@@ -95,6 +95,34 @@ int32_t msbb_witness_check(msbb_witness* w, const uint32_t beta[4], const uint32
  * 128 up to 127, 64 up to 255 (0: the slot file does not fit)] */
 int32_t msbb_system_check_info(const msbb_system* sys, size_t circuit, uint64_t out4[4]);
 
+/* ---- Lookup balance, exact: ms_witness_lookup_balance (include/mstark.h, "Lookup balance") for this configuration - its
+ * definition read over p = 2^31 - 2^27 + 1. Messages are the claims (multiplicity 1) and every (active circuit, row, lookup
+ * slot) of non-zero multiplicity, with the multiplicity and arguments msbb_stage2_build evaluates; tuples are compared after
+ * trailing zeros are stripped; a group's net is the sum of its multiplicities modulo p; origin order is claims by index, then
+ * the circuits in system order, row-major, slot last. It takes no challenges.
+ *   Report: the layout of ms_witness_lookup_balance. summary: [0] messages  [1] groups  [2] unbalanced groups  [3] entries
+ * written = min([2], entries_cap). entries: MS_LB_ENTRY_WORDS words each, the same eight fields ([0] circuit or MS_LB_CLAIMS,
+ * [1] row or claim index, [2] slot, [3] net, canonical and non-zero, [4] members, [5] length of the stripped tuple, [6] where it
+ * starts in args_out - all-ones for a tuple that would end behind args_cap - [7] reserved, 0), in ascending order of first
+ * origin whatever their total number. args_out: the stripped tuples as canonical 4-byte words, packed in entry order.
+ * slot_counts (nullable): sum(num_lookups) + 1 words, per lookup slot in system order and then the claims, the messages that
+ * belong to an unbalanced group; MS_ERR_BUFFER when slots_cap is below that. Every figure is deterministic.
+ *   An unbalanced witness is MS_OK. MS_ERR (text via ms_last_error(), the context stays usable) is for misuse: a host-resident
+ * witness (msbb_witness_create_host); a witness that does not belong to the system; a null w or summary; a null buffer with a
+ * non-zero capacity; 2^32 messages or more (each group's multiplicities are summed in one 64-bit word, exact below that). A
+ * system without lookups and without claims: MS_OK, zeros. The witness is not changed: msbb_prove behind the call writes the
+ * bytes it writes without it.
+ *   Memory: the witness keeps no lookup values, so each active circuit's are swept into temporaries of the call -
+ * 4 x height x (num_lookups + args_width) bytes, plus 4 x height x lookup prefix length of scratch while its sweep runs; the
+ * grouping table takes 32 bytes x cap, cap = the power of two >= max(64, 2 x M), M = claims + sum over the active circuits of
+ * height x num_lookups (134 MB for MulAir at 2^20 rows, M = 2^21), plus M / 8 bytes of marks. An allocation failure is MS_ERR
+ * naming the bytes. MSAMD_LB_HASH_BITS=k (diagnostics, read per call) keeps only the low k bits of the hash, as for
+ * ms_witness_lookup_balance: the report is the same, by a longer way.
+ *   Host waits: one when the witness is balanced; one more, to fetch entries and tuples, when it is not and entries_cap > 0. */
+int32_t msbb_witness_lookup_balance(msbb_witness* w, uint64_t summary[4], uint64_t* entries, size_t entries_cap /* nullable with cap 0 */,
+                                    uint32_t* args_out, size_t args_cap /* nullable with cap 0; canonical values */,
+                                    uint64_t* slot_counts /* nullable */, size_t slots_cap);
+
 /* Writes Proof::to_bytes (src/prover.rs:241-248). stage_ms (optional, 6 doubles) as for ms_prove. */
 int32_t msbb_prove(msbb_system* sys, msbb_witness* w, uint8_t* proof_out, size_t cap, size_t* proof_len, double* stage_ms);
 

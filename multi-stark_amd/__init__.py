@@ -586,17 +586,18 @@ _P = (1 << 64) - (1 << 32) + 1
 
 class BalanceEntry:
     """One unbalanced group of a LookupBalanceReport: .origin = (circuit or "claims", row or claim index, lookup slot) of its
-    first member, .net (canonical, non-zero), .members, .args (the tuple without trailing zeros; None: it did not fit)"""
+    first member, .net (canonical, non-zero), .members, .args (the tuple without trailing zeros; None: it did not fit); p: the
+    field's modulus (default Goldilocks), which only the text reads: a net above p / 2 is printed as negative"""
 
-    def __init__(self, origin, net, members, args):
-        self.origin, self.net, self.members, self.args = origin, net, members, args
+    def __init__(self, origin, net, members, args, p=None):
+        self.origin, self.net, self.members, self.args, self.p = origin, net, members, args, _P if p is None else p
 
     def fields(self):
         return (self.origin, self.net, self.members, self.args)
 
     def line(self, names=None):
         c, r, j = self.origin
-        net = self.net - _P if self.net > _P // 2 else self.net
+        net = self.net - self.p if self.net > self.p // 2 else self.net
         tup = "(?)" if self.args is None else "(%s)" % ", ".join(str(a) for a in self.args)
         if c == "claims":
             where = "claim %d" % r
@@ -607,11 +608,12 @@ class BalanceEntry:
 
 class LookupBalanceReport:
     """What SystemWitness.lookup_balance returns: .ok, .messages, .groups, .unbalanced, .entries (BalanceEntry, ascending first
-    origin, at most as many as asked for), .slot_counts[circuit][slot] and .claims_count (messages of unbalanced groups)"""
+    origin, at most as many as asked for), .slot_counts[circuit][slot] and .claims_count (messages of unbalanced groups); p:
+    the field's modulus (default Goldilocks; babybear.Witness.lookup_balance passes its own)"""
 
-    def __init__(self, messages, groups, unbalanced, entries, slot_counts, claims_count, names=None):
+    def __init__(self, messages, groups, unbalanced, entries, slot_counts, claims_count, names=None, p=None):
         self.messages, self.groups, self.unbalanced, self.entries = messages, groups, unbalanced, entries
-        self.slot_counts, self.claims_count, self.names = slot_counts, claims_count, names
+        self.slot_counts, self.claims_count, self.names, self.p = slot_counts, claims_count, names, _P if p is None else p
         self.ok = unbalanced == 0
 
     def fields(self):

@@ -23,7 +23,8 @@ def exported_symbols():
             "msbb_challenger_create", "msbb_challenger_destroy", "msbb_challenger_observe", "msbb_challenger_observe_digests",
             "msbb_challenger_sample_ext", "msbb_challenger_sample_bits", "msbb_challenger_observe_claims", "msbb_trace_destroy", "msbb_trace_info",
             "msbb_system_preprocessed_mmcs", "msbb_witness_commit_stage1", "msbb_witness_claims_accumulator", "msbb_stage2_build",
-            "msbb_pcs_commit_traces", "msbb_quotient", "msbb_pcs_commit_ldes", "msbb_pcs_open", "msbb_witness_check", "msbb_system_check_info"]
+            "msbb_pcs_commit_traces", "msbb_quotient", "msbb_pcs_commit_ldes", "msbb_pcs_open", "msbb_witness_check", "msbb_system_check_info",
+            "msbb_witness_lookup_balance"]
 
 
 import sys
@@ -98,6 +99,36 @@ class Witness:
             circuits.append(pkg.CircuitCheck(i, words[i], cnt[o:o + roots[i]].copy(), first[o:o + roots[i]].copy(),
                                              names[i] if names else None, origins[i] if origins else None, ext_d=4))
         return pkg.CheckReport(int(verdict.value), circuits, beta, gamma, ext_d=4)
+
+    def lookup_balance(self, entries=64, names=None):
+        """msbb_witness_lookup_balance: every message of the witness grouped by its tuple, exactly (no challenges); the groups
+        whose multiplicities do not cancel modulo p, with where they came from. -> the package's LookupBalanceReport (modulus
+        p) with at most `entries` entries. names (optional, per circuit): labels for the text of the report."""
+        pkg = _pkg()
+        sysm = self.system
+        nl = [sysm.circuit_info(i)["num_lookups"] for i in range(sysm.n_circuits)]
+        total = sum(nl)
+        summary, counts = np.zeros(4, dtype=np.uint64), np.zeros(total + 1, dtype=np.uint64)
+        ent = np.zeros((max(entries, 1), pkg.LB_ENTRY_WORDS), dtype=np.uint64)
+        args_cap = 64 * max(entries, 1)
+        while True:
+            args = np.zeros(args_cap, dtype=np.uint32)
+            _check(_lib().msbb_witness_lookup_balance(self.h, summary.ctypes.data_as(u64p), ent.ctypes.data_as(u64p), C.c_size_t(entries), _p32(args),
+                                                      C.c_size_t(args_cap), counts.ctypes.data_as(u64p), C.c_size_t(total + 1)))
+            n = int(summary[3])
+            need = int(ent[:n, 5].sum())
+            if need <= args_cap:
+                break
+            args_cap = need  # some tuple did not fit: the lengths are known now
+        none = (1 << 64) - 1
+        out = []
+        for e in ent[:n]:
+            origin = ("claims", int(e[1]), 0) if int(e[0]) == none else (int(e[0]), int(e[1]), int(e[2]))
+            a = None if int(e[6]) == none else [int(x) for x in args[int(e[6]):int(e[6]) + int(e[5])]]
+            out.append(pkg.BalanceEntry(origin, int(e[3]), int(e[4]), a, p=P))
+        offs = np.cumsum([0] + nl)
+        slot_counts = [[int(x) for x in counts[offs[i]:offs[i + 1]]] for i in range(sysm.n_circuits)]
+        return pkg.LookupBalanceReport(int(summary[0]), int(summary[1]), int(summary[2]), out, slot_counts, int(counts[total]), names, p=P)
 
     def __init__(self, system, traces, claims_packed, host_resident=False):
         """host_resident: the witness stays in host memory (msbb_witness_create_host) and every proof uploads it - the

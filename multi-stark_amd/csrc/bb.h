@@ -101,6 +101,10 @@ void bb_stage2(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookups
 // whose total is zero). bb_stage2 is this plus the read-back.
 void bb_stage2_async(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookupsDev& lk, const BMat& trace, const BMat* pre, E4 beta,
                      E4 gamma, BMat& out, E4* d_total);
+// the lookup values themselves, which stage 2 evaluates and discards: mult (n x L) and args (n x args_width), row-major
+// Montgomery words; scratch: prefix_len x n words, as in stage 2. One launch, no host wait (bb_balance.hip)
+void bb_lookup_values_async(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookupsDev& lk, size_t args_width, const BMat& trace,
+                            const BMat* pre, u32* scratch, u32* mult, u32* args);
 // sum over the claims of 1 / (beta + fingerprint(gamma, claim)) (src/prover.rs:382-387); data in Montgomery form
 E4 bb_claims_accumulator(Ctx& ctx, const u32* d_data_monty, const u64* d_offs, size_t n, E4 beta, E4 gamma);
 void bb_claims_accumulator_async(Ctx& ctx, const u32* d_data_monty, const u64* d_offs, size_t n, E4 beta, E4 gamma, E4* d_total);  // no read-back

@@ -183,6 +183,11 @@ void witness_check(BSystem& sys, BWitness& wit, E4 beta, E4 gamma, uint32_t* ver
 size_t check_roots(const BCircuit& c);                        // user constraint roots (throws if `zeros` disagrees)
 const BCheckProgram& check_program(BSystem& sys, size_t ci);  // built on first use
 unsigned check_lds_lanes(size_t n_slots);                     // lanes of the thread-per-row LDS form (0: the slot file does not fit)
+// msbb_witness_lookup_balance (bb_balance.hip): every message grouped by its tuple, exactly; entries: entries_cap x
+// MS_LB_ENTRY_WORDS, args_out: canonical words; slot_counts nullable, lookup_balance_slots(sys) + 1 words
+size_t lookup_balance_slots(const BSystem& sys);
+void witness_lookup_balance(BSystem& sys, BWitness& wit, u64 summary[4], u64* entries, size_t entries_cap, u32* args_out, size_t args_cap,
+                            u64* slot_counts);
 // MerkleTreeMmcs::verify_batch for many openings of one commitment, one device thread per opening; everything canonical
 void mmcs_verify_batch_device(Ctx& ctx, const Poseidon2* d_perm, const std::vector<size_t>& heights, const std::vector<size_t>& widths,
                               const u32* cap, unsigned cap_height, size_t n_openings, const u64* indices, const u32* vals, const u32* siblings,

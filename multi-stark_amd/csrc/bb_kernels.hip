@@ -784,6 +784,53 @@ void bb_stage2(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookups
   ctx.d2h(total, d_total.p, sizeof(E4));
 }
 
+// the lookup values stage 2 evaluates and discards, kept (msbb_witness_lookup_balance, bb_balance.hip): the same sweep over the
+// lookup prefix with the same RowView, one thread per row; the multiplicity node of every slot goes to mult[r * L + l] and
+// every argument node to args[r * aw + k], Montgomery words. Row-major, because the grouping kernels number the messages
+// row-major, slot last: 64 consecutive messages are 64 / L rows x L slots, which in this layout are one contiguous run of
+// 64 multiplicities and one of (64 / L) x aw argument words. The strided stores here are paid once; those reads three times.
+struct LookupValuesArgs {
+  const u32 *kind, *na, *nb;
+  unsigned prefix_len;
+  const u32 *lk_mult, *lk_args;
+  unsigned L, aw;
+  const u32* trace;
+  size_t trace_ld;
+  const u32* pre;
+  size_t pre_ld;
+  size_t n;
+  u32 *scratch, *mult, *args;
+};
+__global__ __launch_bounds__(256) void lookup_values_k(LookupValuesArgs p) {
+  size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= p.n) return;
+  size_t rn = r + 1 == p.n ? 0 : r + 1;
+  RowView v;
+  v.pre0 = p.pre ? p.pre + r : nullptr, v.pre1 = p.pre ? p.pre + rn : nullptr, v.pre_ld = p.pre_ld;
+  v.main0 = p.trace + r, v.main1 = p.trace + rn, v.main_ld = p.trace_ld;
+  v.s20 = v.s21 = nullptr, v.s2_ld = 0;
+  v.publics = nullptr;
+  v.is_first = r == 0 ? BB_R1 : 0;
+  v.is_last = r + 1 == p.n ? BB_R1 : 0;
+  v.is_trans = r + 1 == p.n ? 0 : BB_R1;
+  u32* slots = p.scratch + r;
+  sweep(p.kind, p.na, p.nb, p.prefix_len, v, slots, p.n);
+  for (unsigned l = 0; l < p.L; l++) p.mult[r * p.L + l] = slots[(size_t)p.lk_mult[l] * p.n];
+  for (unsigned k = 0; k < p.aw; k++) p.args[r * p.aw + k] = slots[(size_t)p.lk_args[k] * p.n];
+}
+void bb_lookup_values_async(Ctx& ctx, const BProgram& prog, size_t prefix_len, const BLookupsDev& lk, size_t args_width, const BMat& trace,
+                            const BMat* pre, u32* scratch, u32* mult, u32* args) {
+  size_t n = trace.h;
+  if (!n || !lk.L) return;
+  LookupValuesArgs a;
+  a.kind = prog.kind.p, a.na = prog.a.p, a.nb = prog.b.p, a.prefix_len = (unsigned)prefix_len;
+  a.lk_mult = lk.mult.p, a.lk_args = lk.args.p, a.L = (unsigned)lk.L, a.aw = (unsigned)args_width;
+  a.trace = trace.buf.p, a.trace_ld = trace.ld;
+  a.pre = pre ? pre->buf.p : nullptr, a.pre_ld = pre ? pre->ld : 0;
+  a.n = n, a.scratch = scratch, a.mult = mult, a.args = args;
+  lookup_values_k<<<blocks_for(n, 256), 256, 0, ctx.stream>>>(a);
+}
+
 // claims accumulator (src/prover.rs:382-387): sum over the claims of 1 / (beta + fingerprint(gamma, claim))
 __global__ void claims_terms_k(const u32* __restrict__ data, const u64* __restrict__ offs, size_t n, E4 beta, E4 gamma, E4* __restrict__ terms) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

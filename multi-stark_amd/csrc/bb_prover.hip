@@ -1531,6 +1531,19 @@ int32_t msbb_witness_check(msbb_witness* w, const uint32_t beta[4], const uint32
   return MS_OK;
   BB_CATCH
 }
+int32_t msbb_witness_lookup_balance(msbb_witness* w, uint64_t summary[4], uint64_t* entries, size_t entries_cap, uint32_t* args_out,
+                                    size_t args_cap, uint64_t* slot_counts, size_t slots_cap) {
+  BB_TRY
+  if (!w || !summary) throw std::runtime_error("msbb_witness_lookup_balance: null argument");
+  if ((!entries && entries_cap) || (!args_out && args_cap)) throw std::runtime_error("msbb_witness_lookup_balance: null buffer with a non-zero capacity");
+  BWitness& wit = *w->w;
+  BSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  if (slot_counts && slots_cap < lookup_balance_slots(sys) + 1) return MS_ERR_BUFFER;
+  witness_lookup_balance(sys, wit, summary, entries, entries_cap, args_out, args_cap, slot_counts);
+  return MS_OK;
+  BB_CATCH
+}
 int32_t msbb_system_check_info(const msbb_system* sys, size_t circuit, uint64_t out4[4]) {
   BB_TRY
   if (!sys || !out4) throw std::runtime_error("msbb_system_check_info: null argument");
