@@ -42,6 +42,8 @@ pub const MS_CHECK_CIRCUIT_WORDS: usize = 10;
 /// ms_witness_lookup_balance: words per entry; the circuit word of an entry whose first origin is a claim
 pub const MS_LB_ENTRY_WORDS: usize = 8;
 pub const MS_LB_CLAIMS: u64 = !0;
+/// ms_witness_derive_multiplicities: words of its summary
+pub const MS_DM_SUMMARY_WORDS: usize = 6;
 /// msbb_witness_check: the same mask; four accumulator coordinates per circuit
 pub const MSBB_CHECK_CIRCUIT_WORDS: usize = 12;
 
@@ -59,6 +61,14 @@ pub struct ms_dev_matrix {
     /// in elements, both > 0
     pub row_stride: i64,
     pub col_stride: i64,
+}
+
+/// One provider slot of ms_witness_derive_multiplicities: lookup slot `slot` of circuit `circuit`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ms_mult_target {
+    pub circuit: u32,
+    pub slot: u32,
 }
 
 /// Exchanges `ms_prove_sharded` calls back for (device pointers of the context's device; 0 = ok).
@@ -192,6 +202,9 @@ extern "C" {
     pub fn ms_system_check_info(sys: *const ms_system, circuit: usize, out4: *mut u64) -> i32;
     pub fn ms_witness_lookup_balance(w: *mut ms_witness, summary: *mut u64, entries: *mut u64, entries_cap: usize, args_out: *mut u64,
                                      args_cap: usize, slot_counts: *mut u64, slots_cap: usize) -> i32;
+    pub fn ms_system_multiplicity_slot(sys: *const ms_system, circuit: usize, slot: usize, out3: *mut u64) -> i32;
+    pub fn ms_witness_derive_multiplicities(w: *mut ms_witness, targets: *const ms_mult_target, n_targets: usize, summary: *mut u64,
+                                            entries: *mut u64, entries_cap: usize, args_out: *mut u64, args_cap: usize) -> i32;
     pub fn ms_witness_claims_accumulator(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_out: *mut u64) -> i32;
     pub fn ms_stage2_build(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_in: *const u64, accs_out: *mut u64,
                            traces_out: *mut *mut ms_trace) -> i32;

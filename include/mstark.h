@@ -284,6 +284,59 @@ int32_t ms_witness_lookup_balance(ms_witness* w, uint64_t summary[4], uint64_t* 
                                   uint64_t* args_out, size_t args_cap /* nullable with cap 0 */, uint64_t* slot_counts /* nullable */,
                                   size_t slots_cap);
 
+/* ---- Table multiplicity columns derived on the device. Every lookup system has table circuits with a main-trace column that
+ * counts how often each table row is pulled (ByteTable column 0, the four ByteCS columns, RangeTable column 0); witness builders
+ * fill it on the host with a histogram of the consumers' messages. For a witness whose traces were produced in HBM
+ * (ms_witness_create_device) this call computes those columns there, from all other messages of the witness: the grouping of
+ * ms_witness_lookup_balance followed by a write instead of a report. Goldilocks / BLAKE3 configuration.
+ *   Definition. Messages, stripped tuples, origin order and first origin are those of ms_witness_lookup_balance above.
+ *   A TARGET is a lookup slot (c, j) named by the caller. It is ELIGIBLE when (1) its compiled multiplicity node is OP_VAR on the
+ * main trace at offset 0, column m (a PUSH, sign s = +1), or OP_NEG of such a node (a PULL, s = -1), and (2) column m of circuit c
+ * is read by no other lookup expression of that circuit: no argument of any slot (the target's own included) and no other slot's
+ * multiplicity, at either row offset, following the node program (not the authoring form). Column m is then a DERIVED column.
+ * User constraints may read it; that is the caller's business, and ms_witness_check will tell. ms_system_multiplicity_slot
+ * classifies a slot. Misuse (MS_ERR): two targets that share a derived column (the same target named twice is that); a derived
+ * column that another target's expressions read (which (2) already excludes); an ineligible or out-of-range target.
+ *   DEMAND is every message of the witness that does not come from a target slot: the claims, and every non-target slot of
+ * every active circuit; multiplicity 0 does not exist. D(t) is the sum modulo p of the demand multiplicities with stripped
+ * tuple t. For a tuple t its PROVIDER is the target row (c, r, j) of smallest origin whose stripped tuple is t (a target row's
+ * tuple depends only on its arguments, never on the derived column). The call writes, for every target row,
+ *   at the provider: column m of row r = v with s v + D(t) = 0 (mod p), canonical - v = D(t) for a pull, p - D(t) for a push,
+ *     0 when D(t) = 0;
+ *   at every other target row (a later row with the same tuple - a DUPLICATE - or one whose tuple has no demand): 0.
+ * What the derived columns held before is ignored and overwritten. A group with D(t) != 0 and no target row is UNSERVED.
+ * Postcondition: the witness is balanced, in the sense of ms_witness_lookup_balance, exactly when nothing is unserved.
+ *   Held lookup values. Where the witness holds lookup values for circuit c - made by from_stage_1 or supplied by the caller at
+ * ms_witness_create - the multiplicity of slot j is updated to s v in the same call, so that ms_prove, ms_stage2_build,
+ * ms_witness_check and ms_witness_lookup_balance behind the call see one consistent witness. Arguments are untouched. Nothing
+ * else in the witness changes: other columns, other traces and the claims stay byte-identical.
+ *   Report. summary: [0] demand messages  [1] demand groups  [2] served groups with D != 0  [3] unserved groups  [4] duplicate
+ * target rows: target rows that are not the provider although an earlier target row has their tuple, demanded or not
+ * [5] entries written = min([3], entries_cap). entries / args_out (each nullable with capacity 0): the unserved groups with the
+ * smallest first origins among their demand members, ascending, in the MS_LB_ENTRY_WORDS layout of ms_witness_lookup_balance:
+ * circuit (or MS_LB_CLAIMS), row, slot, net = D(t), demand members, tuple length, tuple start in args_out (all-ones: it would end
+ * behind args_cap), 0. Every written value and every figure is deterministic: nothing depends on thread order or on the hash.
+ *   Unserved demand is MS_OK. n_targets == 0 is MS_OK: a pure demand count with no writes. A target circuit that is inactive
+ * (height 0) is not an error: it has no rows, so its demand is unserved. MS_ERR (text via ms_last_error(), the context stays
+ * usable; each of these is refused before anything is written): a host-resident witness; a witness with circuits or claims held by another rank; a null w or
+ * summary; null targets with n_targets > 0; a null buffer with a non-zero capacity; misuse of targets as above; a circuit whose
+ * lookup values the witness does not hold and whose lookup prefix does not fit the device sweep.
+ *   Memory: the grouping table takes 48 bytes x cap, cap = the power of two >= max(64, 2 x M), M = claims + sum over the active
+ * circuits of height x num_lookups (target slots included), plus 8 bytes per target row and M / 8 bytes of marks; lookup values
+ * the witness does not hold are computed into temporaries of the call. An allocation failure is MS_ERR naming the bytes.
+ * MSAMD_LB_HASH_BITS as for ms_witness_lookup_balance.
+ *   Host waits: one, for the summary; one more, to fetch entries and tuples, when something is unserved and entries_cap > 0. */
+/* out3 = [eligibility: 0 eligible, 1 multiplicity is not one main column at offset 0 (optionally negated),
+ *         2 that column is read by another lookup expression of the circuit; column m; sign: 0 push, 1 pull]
+ * (column and sign are 0 with eligibility 1) */
+int32_t ms_system_multiplicity_slot(const ms_system* sys, size_t circuit, size_t slot, uint64_t out3[3]);
+
+typedef struct ms_mult_target { uint32_t circuit, slot; } ms_mult_target;
+#define MS_DM_SUMMARY_WORDS 6
+int32_t ms_witness_derive_multiplicities(ms_witness* w, const ms_mult_target* targets, size_t n_targets,
+                                         uint64_t summary[MS_DM_SUMMARY_WORDS], uint64_t* entries, size_t entries_cap /* nullable with cap 0 */,
+                                         uint64_t* args_out, size_t args_cap /* nullable with cap 0 */);
+
 /* ---- System::prove_multiple_claims (src/prover.rs:290-603). Writes Proof::to_bytes (src/prover.rs:241-248).
  * stage_ms (optional, 6 doubles): stage1_commit, lookup_construction, stage2_commit, quotient, fri_open, total —
  * the reference's span names (src/prover.rs:336-538). Returns MS_ERR_BUFFER with *proof_len = needed size if

@@ -52,7 +52,8 @@ def exported_symbols():
             "ms_challenger_sample_bits", "ms_stage2_trace", "ms_claims_accumulator",
             "ms_quotient_values", "ms_field_op", "ms_trace_destroy", "ms_trace_info", "ms_system_preprocessed_mmcs",
             "ms_witness_commit_stage1", "ms_challenger_observe_claims", "ms_witness_claims_accumulator", "ms_stage2_build",
-            "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes", "ms_witness_check", "ms_system_check_info", "ms_witness_lookup_balance"]
+            "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes", "ms_witness_check", "ms_system_check_info", "ms_witness_lookup_balance",
+            "ms_system_multiplicity_slot", "ms_witness_derive_multiplicities"]
 
 
 # ms_system_circuit_kernels / msbb_system_circuit_kernels (MS_KERNEL_* in include/mstark.h)
@@ -635,8 +636,64 @@ class LookupBalanceReport:
         return "\n".join(out)
 
 
+DM_SUMMARY_WORDS = 6  # MS_DM_SUMMARY_WORDS of include/mstark.h
+
+
+class MultTarget(C.Structure):
+    """ms_mult_target (include/mstark.h): a provider slot of SystemWitness.derive_multiplicities"""
+    _fields_ = [("circuit", C.c_uint32), ("slot", C.c_uint32)]
+
+
+class MultiplicityReport:
+    """What SystemWitness.derive_multiplicities returns: .demand_messages, .demand_groups, .served (groups of non-zero demand that
+    found a provider), .unserved (those that found none), .duplicates (target rows that repeat an earlier target row's tuple),
+    .entries (BalanceEntry of the unserved groups, ascending first origin, at most as many as asked for); .ok: nothing is unserved"""
+
+    def __init__(self, demand_messages, demand_groups, served, unserved, duplicates, entries):
+        self.demand_messages, self.demand_groups, self.served, self.unserved = demand_messages, demand_groups, served, unserved
+        self.duplicates, self.entries = duplicates, entries
+        self.ok = unserved == 0
+
+    def fields(self):
+        """everything, as plain values (what a model of the call reproduces)"""
+        return (self.demand_messages, self.demand_groups, self.served, self.unserved, self.duplicates, [e.fields() for e in self.entries])
+
+    def __str__(self):
+        head = "%d demand messages in %d groups: %d served, %d unserved; %d duplicate target rows" % (
+            self.demand_messages, self.demand_groups, self.served, self.unserved, self.duplicates)
+        out = [head] + ["unserved " + e.line() for e in self.entries]
+        if self.unserved > len(self.entries):
+            out.append("... and %d more unserved groups" % (self.unserved - len(self.entries)))
+        return "\n".join(out)
+
+
 class SystemWitness:
     """Device-resident SystemWitness + claims (ms_witness). Built by `System.witness`."""
+
+    def derive_multiplicities(self, targets, entries=64):
+        """ms_witness_derive_multiplicities: targets = [(circuit, lookup slot)], the provider slots whose multiplicity is one
+        main-trace column (System.multiplicity_slot tells); that column is overwritten, on the device, with what the demand of
+        all other messages of the witness asks of each row, and the held lookup values follow. -> MultiplicityReport with at
+        most `entries` entries for demand no target row serves."""
+        tg = (MultTarget * max(len(targets), 1))(*[MultTarget(int(c), int(j)) for c, j in targets])
+        summary = np.zeros(DM_SUMMARY_WORDS, dtype=np.uint64)
+        ent = np.zeros((max(entries, 1), LB_ENTRY_WORDS), dtype=np.uint64)
+        args_cap = 64 * max(entries, 1)
+        while True:  # (a second call writes the same bytes: it is only made when some tuple did not fit)
+            args = np.zeros(args_cap, dtype=np.uint64)
+            _check(lib().ms_witness_derive_multiplicities(self.h, tg, C.c_size_t(len(targets)), _p(summary), _p(ent), C.c_size_t(entries), _p(args),
+                                                          C.c_size_t(args_cap)))
+            n = int(summary[5])
+            need = int(ent[:n, 5].sum())
+            if need <= args_cap:
+                break
+            args_cap = need
+        out = []
+        for e in ent[:n]:
+            origin = ("claims", int(e[1]), 0) if int(e[0]) == _NONE else (int(e[0]), int(e[1]), int(e[2]))
+            a = None if int(e[6]) == _NONE else [int(x) for x in args[int(e[6]):int(e[6]) + int(e[5])]]
+            out.append(BalanceEntry(origin, int(e[3]), int(e[4]), a))
+        return MultiplicityReport(*(int(x) for x in summary[:5]), out)
 
     def lookup_balance(self, entries=64, names=None):
         """ms_witness_lookup_balance: every message of the witness grouped by its tuple, exactly (no challenges); the groups
@@ -779,6 +836,14 @@ class System:
         o = np.zeros(4, dtype=np.uint64)
         _check(lib().ms_system_check_info(self.h, C.c_size_t(ci), _p(o)))
         return dict(zip(["roots", "slots", "wave_steps", "lds_lanes"], (int(x) for x in o)))
+
+    def multiplicity_slot(self, circuit, slot):
+        """ms_system_multiplicity_slot: may lookup slot `slot` of `circuit` be a target of SystemWitness.derive_multiplicities?
+        eligibility 0 yes / 1 its multiplicity is not one main-trace column (optionally negated) / 2 that column is read by
+        another lookup expression of the circuit; column: the derived column; pull: the multiplicity is the negated column"""
+        o = np.zeros(3, dtype=np.uint64)
+        _check(lib().ms_system_multiplicity_slot(self.h, C.c_size_t(circuit), C.c_size_t(slot), _p(o)))
+        return {"eligibility": int(o[0]), "column": int(o[1]), "pull": bool(o[2])}
 
     def circuit_kernels(self, ci):
         """ms_system_circuit_kernels: the mask of KERNEL_* bits of the kernels generated and compiled for circuit `ci` (0 = the

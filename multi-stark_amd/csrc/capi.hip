@@ -385,6 +385,26 @@ int32_t ms_witness_lookup_balance(ms_witness* w, uint64_t summary[4], uint64_t* 
   return MS_OK;
   MS_CATCH
 }
+int32_t ms_system_multiplicity_slot(const ms_system* sys, size_t ci, size_t slot, uint64_t out3[3]) {
+  MS_TRY if (!sys || !out3) throw std::runtime_error("ms_system_multiplicity_slot: null argument");
+  const HSystem& s = *sys->sys;
+  if (ci >= s.circuits.size()) throw std::runtime_error("circuit index out of range");
+  multiplicity_slot(s.circuits[ci], slot, out3);
+  return MS_OK;
+  MS_CATCH
+}
+int32_t ms_witness_derive_multiplicities(ms_witness* w, const ms_mult_target* targets, size_t n_targets, uint64_t summary[MS_DM_SUMMARY_WORDS],
+                                         uint64_t* entries, size_t entries_cap, uint64_t* args_out, size_t args_cap) {
+  MS_TRY if (!w || !summary || (!targets && n_targets)) throw std::runtime_error("ms_witness_derive_multiplicities: null argument");
+  if ((!entries && entries_cap) || (!args_out && args_cap))
+    throw std::runtime_error("ms_witness_derive_multiplicities: null buffer with a non-zero capacity");
+  HWitness& wit = *w->w;
+  HSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  witness_derive_multiplicities(sys, wit, targets, n_targets, summary, entries, entries_cap, args_out, args_cap);
+  return MS_OK;
+  MS_CATCH
+}
 int32_t ms_system_check_info(const ms_system* sys, size_t ci, uint64_t out4[4]) {
   MS_TRY if (!sys || !out4) throw std::runtime_error("ms_system_check_info: null argument");
   const HSystem& s = *sys->sys;

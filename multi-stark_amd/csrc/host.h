@@ -227,6 +227,11 @@ unsigned check_lds_lanes(size_t n_slots);       // lanes per workgroup of the ch
 void witness_lookup_balance(HSystem& sys, HWitness& wit, u64 summary[4], u64* entries, size_t entries_cap, u64* args_out, size_t args_cap,
                             u64* slot_counts);
 size_t lookup_balance_slots(const HSystem& sys);  // sum of num_lookups over every circuit of the system
+// ms_witness_derive_multiplicities (multiplicity.hip): the derived columns of the target slots written from the demand of all
+// other messages; entries / args_out as for the balance. One host wait, a second one for the entries when demand is unserved
+void witness_derive_multiplicities(HSystem& sys, HWitness& wit, const ms_mult_target* targets, size_t n_targets, u64 summary[MS_DM_SUMMARY_WORDS],
+                                   u64* entries, size_t entries_cap, u64* args_out, size_t args_cap);
+void multiplicity_slot(const HCircuit& c, size_t slot, u64 out3[3]);  // ms_system_multiplicity_slot: [eligibility, column, pull]
 void field_op(Ctx& ctx, int op, const u64* a, const u64* b, size_t n, u64* out);
 
 }  // namespace msamd
