@@ -12,6 +12,16 @@
  * order: a system keeps its context alive, a witness its system, an mmcs its context (the memory is released when the
  * last dependent handle is destroyed).
  *
+ * Threads: one ms_ctx (with its systems and witnesses) is driven by one thread at a time. Several contexts, of one device or of
+ * several, each driven by its own host thread, are independent of each other - in this configuration and in the BabyBear /
+ * Poseidon2 one (mstark_bb.h) alike; ms_last_error() is per thread. Contexts of one device share, behind locks of the
+ * library's own: the BabyBear twiddle tables (per device and size; a table is published only once it has been filled), the
+ * hiprtc code objects of the generated circuit kernels and their disk cache (per process), the pool of host threads that
+ * narrows host-resident traces (per device, one job at a time), the page-lock counts of caller memory handed to
+ * ms_witness_create_host / msbb_witness_create_host (per range: two contexts may be given the same buffers), and the per-device
+ * Poseidon2 permutation of the BabyBear PCS-level calls. The last one is the exception to the independence:
+ * msbb_set_poseidon2 must not be called while another context of that device is inside a PCS-level msbb_* call.
+ *
  * What each group replaces in /root/reference:
  *   ms_system_*    System::new + ProverKey                      src/system.rs:115-203 (preprocessed commit :190-195)
  *   ms_witness_*   SystemWitness / from_stage_1                 src/system.rs:225-328 (host-resident: the witness argument

@@ -63,12 +63,19 @@ void bb_download_rows(Ctx& ctx, const BMat& m, bool bitrev_rows, u32* host) {
 // ------------------------------------------------------------------ transforms
 // Twiddle table of the order-2^n root: w^j, j < 2^(n-1), Montgomery form. Cached per size in a process-wide map keyed
 // by (device, n); the tables are small next to the matrices (half a column).
+// A table is shared by every context of its device, and those contexts run on streams that nothing orders against each
+// other. So a table enters the map only once its fill has completed on the device: the creating context fills it on its
+// own stream, records an event behind the fill and waits for that event on the host, all under the mutex. Whoever finds
+// a pointer in the map may read the table from any stream. The wait happens once per size per process and does not go
+// through Ctx::sync() (it delivers no read-backs and is not counted in host_syncs).
 __global__ void twiddles_k(u32* out, size_t count, u32 w) {
   size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j < count) out[j] = bb_pow(w, j);
 }
 struct TwCache {
-  std::mutex mu;  // contexts of different devices may be driven from different host threads
+  // contexts, of one device or of several, may be driven from different host threads: the mutex guards the map and is
+  // held across the creation of a table, so a second context that needs the same size waits for the finished table
+  std::mutex mu;
   std::map<std::pair<int, unsigned>, u32*> t;
 };
 static TwCache& tw_cache() {
@@ -83,7 +90,21 @@ static const u32* twiddles(Ctx& ctx, unsigned log_n) {
   size_t count = log_n ? (size_t(1) << (log_n - 1)) : 1;
   u32* p = nullptr;
   HIP_CHECK(hipMalloc(&p, count * 4));
-  twiddles_k<<<blocks_for(count, 256), 256, 0, ctx.stream>>>(p, count, bb_two_adic_generator(log_n));
+  hipEvent_t filled = nullptr;
+  hipError_t e = hipEventCreateWithFlags(&filled, hipEventDisableTiming);
+  if (e == hipSuccess) {
+    twiddles_k<<<blocks_for(count, 256), 256, 0, ctx.stream>>>(p, count, bb_two_adic_generator(log_n));
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(filled, ctx.stream);
+    // waited for even after a failed record or launch check: nothing may still write the table when it is freed below
+    hipError_t w = e == hipSuccess ? hipEventSynchronize(filled) : hipStreamSynchronize(ctx.stream);
+    if (e == hipSuccess) e = w;
+    (void)hipEventDestroy(filled);
+  }
+  if (e != hipSuccess) {  // nothing is published; the next caller tries again
+    (void)hipFree(p);
+    HIP_CHECK(e);
+  }
   tw_cache().t[key] = p;
   return p;
 }
