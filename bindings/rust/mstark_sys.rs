@@ -241,6 +241,10 @@ extern "C" {
     pub fn msbb_system_check_info(sys: *const msbb_system, circuit: usize, out4: *mut u64) -> i32;
     pub fn msbb_witness_lookup_balance(w: *mut msbb_witness, summary: *mut u64, entries: *mut u64, entries_cap: usize, args_out: *mut u32,
                                        args_cap: usize, slot_counts: *mut u64, slots_cap: usize) -> i32;
+    pub fn msbb_system_multiplicity_slot(sys: *const msbb_system, circuit: usize, slot: usize, out3: *mut u64) -> i32;
+    pub fn msbb_witness_derive_multiplicities(w: *mut msbb_witness, targets: *const ms_mult_target, n_targets: usize, summary: *mut u64,
+                                              entries: *mut u64, entries_cap: usize, args_out: *mut u32, args_cap: usize) -> i32;
+    pub fn msbb_witness_trace(w: *mut msbb_witness, circuit: usize, out: *mut u32, cap_words: usize, n_words: *mut usize) -> i32;
     pub fn msbb_prove(sys: *mut msbb_system, w: *mut msbb_witness, proof_out: *mut u8, cap: usize, proof_len: *mut usize,
                       stage_ms: *mut f64) -> i32;
     pub fn msbb_verify(sys: *mut msbb_system, n_claims: usize, claim_offsets: *const u64, claim_data: *const u32, proof: *const u8,

@@ -123,6 +123,41 @@ int32_t msbb_witness_lookup_balance(msbb_witness* w, uint64_t summary[4], uint64
                                     uint32_t* args_out, size_t args_cap /* nullable with cap 0; canonical values */,
                                     uint64_t* slot_counts /* nullable */, size_t slots_cap);
 
+/* ---- Table multiplicity columns derived on the device: ms_witness_derive_multiplicities (include/mstark.h, "Table multiplicity
+ * columns") for this configuration - its definition read over p = 2^31 - 2^27 + 1, with the same notions: target, eligibility,
+ * demand D(t), provider (the target row of smallest origin with the tuple), duplicates, unserved groups. Messages, stripped tuples
+ * and origin order are those of msbb_witness_lookup_balance above. ms_mult_target, the summary words - [0] demand messages
+ * [1] demand groups  [2] served groups with D != 0  [3] unserved groups  [4] duplicate target rows  [5] entries written = min([3],
+ * entries_cap) - and the entries' layout and order are those of mstark.h. What differs from the Goldilocks call:
+ *   Values cross the ABI as canonical u32: args_out holds the stripped tuples of the unserved groups as 4-byte words.
+ *   Storage: the library's copy of a trace is a column-major matrix of Montgomery words. The provider's cell of column m receives
+ * v - D(t) for a pull, (p - D(t)) mod p for a push - in that form, every other target row 0; msbb_witness_trace shows the
+ * canonical values.
+ *   No held lookup values: a witness of this configuration holds none - msbb_prove, msbb_stage2_build, msbb_witness_check and
+ * msbb_witness_lookup_balance each compute them from the traces - so there is nothing beside the column to update, and every call
+ * behind this one sees the derived column. Other columns, other traces and the claims stay byte-identical.
+ *   Message limit: 2^32 messages or more (target rows count) is MS_ERR, as for msbb_witness_lookup_balance: a group's canonical
+ * multiplicities are summed in one 64-bit word, exact below that.
+ *   Unserved demand, n_targets == 0 (a pure demand count with no writes) and an inactive target circuit are MS_OK. MS_ERR (text
+ * via ms_last_error(), the context stays usable; each is refused before anything is written): a host-resident witness; a witness
+ * that does not belong to the system; a null w or summary; null targets with n_targets > 0; a null buffer with a non-zero
+ * capacity; a target that is out of range, not eligible, or that shares its derived column with an earlier target.
+ *   Memory: the grouping table takes 40 bytes x cap, cap = the power of two >= max(64, 2 x M), M = claims + sum over the active
+ * circuits of height x num_lookups (target slots included) - the four arrays of the balance and one word per slot for the
+ * provider - plus 8 bytes per target row, M / 8 bytes of marks and the sweep temporaries of msbb_witness_lookup_balance. An
+ * allocation failure is MS_ERR naming the bytes. MSAMD_LB_HASH_BITS as for msbb_witness_lookup_balance.
+ *   Host waits: one, for the summary; one more, to fetch entries and tuples, when something is unserved and entries_cap > 0. */
+/* the three numbers of ms_system_multiplicity_slot: [eligibility, column m, sign: 0 push, 1 pull]; one classifier serves both
+ * configurations, as it reads the node program only */
+int32_t msbb_system_multiplicity_slot(const msbb_system* sys, size_t circuit, size_t slot, uint64_t out3[3]);
+int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target* targets, size_t n_targets,
+                                           uint64_t summary[MS_DM_SUMMARY_WORDS], uint64_t* entries, size_t entries_cap /* nullable with cap 0 */,
+                                           uint32_t* args_out, size_t args_cap /* nullable with cap 0; canonical values */);
+/* Diagnostics, as ms_witness_trace: one stage-1 trace of a device-resident witness read back, height x main_width, row-major,
+ * canonical u32. MS_ERR_BUFFER with *n_words = the needed size; an inactive circuit: 0 words, MS_OK. A host-resident witness or
+ * an out-of-range circuit: MS_ERR. */
+int32_t msbb_witness_trace(msbb_witness* w, size_t circuit, uint32_t* out, size_t cap_words, size_t* n_words);
+
 /* Writes Proof::to_bytes (src/prover.rs:241-248). stage_ms (optional, 6 doubles) as for ms_prove. */
 int32_t msbb_prove(msbb_system* sys, msbb_witness* w, uint8_t* proof_out, size_t cap, size_t* proof_len, double* stage_ms);
 

@@ -24,7 +24,7 @@ def exported_symbols():
             "msbb_challenger_sample_ext", "msbb_challenger_sample_bits", "msbb_challenger_observe_claims", "msbb_trace_destroy", "msbb_trace_info",
             "msbb_system_preprocessed_mmcs", "msbb_witness_commit_stage1", "msbb_witness_claims_accumulator", "msbb_stage2_build",
             "msbb_pcs_commit_traces", "msbb_quotient", "msbb_pcs_commit_ldes", "msbb_pcs_open", "msbb_witness_check", "msbb_system_check_info",
-            "msbb_witness_lookup_balance"]
+            "msbb_witness_lookup_balance", "msbb_system_multiplicity_slot", "msbb_witness_derive_multiplicities", "msbb_witness_trace"]
 
 
 import sys
@@ -130,6 +130,45 @@ class Witness:
         slot_counts = [[int(x) for x in counts[offs[i]:offs[i + 1]]] for i in range(sysm.n_circuits)]
         return pkg.LookupBalanceReport(int(summary[0]), int(summary[1]), int(summary[2]), out, slot_counts, int(counts[total]), names, p=P)
 
+    def derive_multiplicities(self, targets, entries=64):
+        """msbb_witness_derive_multiplicities: targets = [(circuit, lookup slot)], the provider slots whose multiplicity is one
+        main-trace column (System.multiplicity_slot tells); that column is overwritten, on the device, with what the demand of
+        all other messages of the witness asks of each row. -> the package's MultiplicityReport (entries with modulus p) with at
+        most `entries` entries for demand no target row serves."""
+        pkg = _pkg()
+        tg = (pkg.MultTarget * max(len(targets), 1))(*[pkg.MultTarget(int(c), int(j)) for c, j in targets])
+        summary = np.zeros(pkg.DM_SUMMARY_WORDS, dtype=np.uint64)
+        ent = np.zeros((max(entries, 1), pkg.LB_ENTRY_WORDS), dtype=np.uint64)
+        args_cap = 64 * max(entries, 1)
+        while True:  # (a second call writes the same bytes: it is only made when some tuple did not fit)
+            args = np.zeros(args_cap, dtype=np.uint32)
+            _check(_lib().msbb_witness_derive_multiplicities(self.h, tg, C.c_size_t(len(targets)), summary.ctypes.data_as(u64p), ent.ctypes.data_as(u64p),
+                                                             C.c_size_t(entries), _p32(args), C.c_size_t(args_cap)))
+            n = int(summary[5])
+            need = int(ent[:n, 5].sum())
+            if need <= args_cap:
+                break
+            args_cap = need
+        none = (1 << 64) - 1
+        out = []
+        for e in ent[:n]:
+            origin = ("claims", int(e[1]), 0) if int(e[0]) == none else (int(e[0]), int(e[1]), int(e[2]))
+            a = None if int(e[6]) == none else [int(x) for x in args[int(e[6]):int(e[6]) + int(e[5])]]
+            out.append(pkg.BalanceEntry(origin, int(e[3]), int(e[4]), a, p=P))
+        return pkg.MultiplicityReport(*(int(x) for x in summary[:5]), out)
+
+    def trace(self, circuit):
+        """one stage-1 trace of a device-resident witness read back (msbb_witness_trace): height x main_width, uint32, canonical"""
+        need = C.c_size_t()
+        rc = _lib().msbb_witness_trace(self.h, C.c_size_t(circuit), None, C.c_size_t(0), C.byref(need))
+        if rc != -3:
+            _check(rc)
+        width = self.system.circuit_info(circuit)["main_width"]
+        out = np.zeros((need.value // width, width), dtype=np.uint32)
+        if need.value:
+            _check(_lib().msbb_witness_trace(self.h, C.c_size_t(circuit), _p32(out), C.c_size_t(out.size), C.byref(need)))
+        return out
+
     def __init__(self, system, traces, claims_packed, host_resident=False):
         """host_resident: the witness stays in host memory (msbb_witness_create_host) and every proof uploads it - the
         reference's timed region; the arrays are kept alive (and page-locked) by this object"""
@@ -190,6 +229,14 @@ class System:
         o = np.zeros(4, dtype=np.uint64)
         _check(_lib().msbb_system_check_info(self.h, C.c_size_t(ci), o.ctypes.data_as(u64p)))
         return dict(zip(["roots", "slots", "wave_steps", "lds_lanes"], (int(x) for x in o)))
+
+    def multiplicity_slot(self, circuit, slot):
+        """msbb_system_multiplicity_slot: may lookup slot `slot` of `circuit` be a target of Witness.derive_multiplicities?
+        eligibility 0 yes / 1 its multiplicity is not one main-trace column (optionally negated) / 2 that column is read by
+        another lookup expression of the circuit; column: the derived column; pull: the multiplicity is the negated column"""
+        o = np.zeros(3, dtype=np.uint64)
+        _check(_lib().msbb_system_multiplicity_slot(self.h, C.c_size_t(circuit), C.c_size_t(slot), o.ctypes.data_as(u64p)))
+        return {"eligibility": int(o[0]), "column": int(o[1]), "pull": bool(o[2])}
 
     def circuit_kernels(self, ci):
         """msbb_system_circuit_kernels: KERNEL_QUOTIENT when the circuit's quotient kernel was generated and compiled, else 0"""

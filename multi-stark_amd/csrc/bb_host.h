@@ -5,6 +5,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "../../include/mstark.h"
 #include "bb.h"
 
 namespace msbb {
@@ -188,6 +189,11 @@ unsigned check_lds_lanes(size_t n_slots);                     // lanes of the th
 size_t lookup_balance_slots(const BSystem& sys);
 void witness_lookup_balance(BSystem& sys, BWitness& wit, u64 summary[4], u64* entries, size_t entries_cap, u32* args_out, size_t args_cap,
                             u64* slot_counts);
+// msbb_witness_derive_multiplicities (bb_multiplicity.hip): the derived columns of the target slots written from the demand of
+// all other messages; entries / args_out as for the balance. One host wait, a second one for the entries when demand is unserved
+void witness_derive_multiplicities(BSystem& sys, BWitness& wit, const ms_mult_target* targets, size_t n_targets, u64 summary[MS_DM_SUMMARY_WORDS],
+                                   u64* entries, size_t entries_cap, u32* args_out, size_t args_cap);
+void multiplicity_slot(const BCircuit& c, size_t slot, u64 out3[3]);  // msbb_system_multiplicity_slot: [eligibility, column, pull]
 // MerkleTreeMmcs::verify_batch for many openings of one commitment, one device thread per opening; everything canonical
 void mmcs_verify_batch_device(Ctx& ctx, const Poseidon2* d_perm, const std::vector<size_t>& heights, const std::vector<size_t>& widths,
                               const u32* cap, unsigned cap_height, size_t n_openings, const u64* indices, const u32* vals, const u32* siblings,

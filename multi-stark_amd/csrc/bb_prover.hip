@@ -1544,6 +1544,48 @@ int32_t msbb_witness_lookup_balance(msbb_witness* w, uint64_t summary[4], uint64
   return MS_OK;
   BB_CATCH
 }
+int32_t msbb_system_multiplicity_slot(const msbb_system* sys, size_t circuit, size_t slot, uint64_t out3[3]) {
+  BB_TRY
+  if (!sys || !out3) throw std::runtime_error("msbb_system_multiplicity_slot: null argument");
+  const BSystem& s = *sys->sys;
+  if (circuit >= s.circuits.size()) throw std::runtime_error("circuit index out of range");
+  multiplicity_slot(s.circuits[circuit], slot, out3);
+  return MS_OK;
+  BB_CATCH
+}
+int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target* targets, size_t n_targets, uint64_t summary[MS_DM_SUMMARY_WORDS],
+                                           uint64_t* entries, size_t entries_cap, uint32_t* args_out, size_t args_cap) {
+  BB_TRY
+  if (!w || !summary || (!targets && n_targets)) throw std::runtime_error("msbb_witness_derive_multiplicities: null argument");
+  if ((!entries && entries_cap) || (!args_out && args_cap))
+    throw std::runtime_error("msbb_witness_derive_multiplicities: null buffer with a non-zero capacity");
+  BWitness& wit = *w->w;
+  BSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  witness_derive_multiplicities(sys, wit, targets, n_targets, summary, entries, entries_cap, args_out, args_cap);
+  return MS_OK;
+  BB_CATCH
+}
+int32_t msbb_witness_trace(msbb_witness* w, size_t circuit, uint32_t* out, size_t cap_words, size_t* n_words) {
+  BB_TRY
+  if (!w || !n_words) throw std::runtime_error("msbb_witness_trace: null argument");
+  BWitness& wit = *w->w;
+  if (wit.host_resident) throw std::runtime_error("msbb_witness_trace: a host-resident witness keeps its traces in the caller's buffers");
+  if (circuit >= wit.heights.size()) throw std::runtime_error("msbb_witness_trace: no such circuit");
+  const BMat& t = wit.traces[circuit];
+  const size_t words = wit.heights[circuit] * wit.sys->circuits[circuit].main_width;
+  if (words && (!t.buf.p || t.h != wit.heights[circuit] || t.w != wit.sys->circuits[circuit].main_width))
+    throw std::runtime_error("msbb_witness_trace: this circuit has no trace on this device");
+  *n_words = words;
+  if (words > cap_words) return MS_ERR_BUFFER;
+  if (!words) return MS_OK;
+  if (!out) throw std::runtime_error("msbb_witness_trace: null output");
+  Ctx& ctx = *wit.sys->ctx;
+  HIP_CHECK(hipSetDevice(ctx.device));
+  bb_download_rows(ctx, t, false, out);
+  return MS_OK;
+  BB_CATCH
+}
 int32_t msbb_system_check_info(const msbb_system* sys, size_t circuit, uint64_t out4[4]) {
   BB_TRY
   if (!sys || !out4) throw std::runtime_error("msbb_system_check_info: null argument");

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "lb_dev.h"
+#include "mult_slot.h"
 
 namespace msamd {
 namespace {
@@ -151,44 +152,10 @@ __global__ __launch_bounds__(256) void dm_write_k(LbTab t, const DmTgt* tg, u32 
   if ((threadIdx.x & 63) == 0 && b) atomicAdd((unsigned long long*)&counters[DM_C_DUPLICATES], (unsigned long long)__popcll(b));
 }
 
-// every node a lookup expression rooted at `root` reads
-void dm_reach(const HCircuit& c, uint32_t root, std::vector<uint8_t>& seen) {
-  std::vector<uint32_t> todo{root};
-  while (!todo.empty()) {
-    const uint32_t n = todo.back();
-    todo.pop_back();
-    if (n >= c.nodes.size() || seen[n]) continue;
-    seen[n] = 1;
-    const PNode& nd = c.nodes[n];
-    if (nd.kind == OP_ADD || nd.kind == OP_SUB || nd.kind == OP_MUL) todo.push_back((uint32_t)nd.a), todo.push_back((uint32_t)nd.b);
-    if (nd.kind == OP_NEG) todo.push_back((uint32_t)nd.a);
-  }
-}
-
 }  // namespace
 
-void multiplicity_slot(const HCircuit& c, size_t slot, u64 out3[3]) {
-  if (slot >= c.lookups.size()) throw std::runtime_error("lookup slot out of range");
-  out3[0] = 1, out3[1] = 0, out3[2] = 0;
-  uint32_t n = c.lookups[slot].first;
-  if (n < c.nodes.size() && c.nodes[n].kind == OP_NEG) out3[2] = 1, n = (uint32_t)c.nodes[n].a;
-  if (n >= c.nodes.size()) return;
-  const PNode& var = c.nodes[n];
-  if (var.kind != OP_VAR || var.source != 1 || var.offset != 0) {
-    out3[2] = 0;
-    return;
-  }
-  out3[1] = var.a;
-  // the other lookup expressions of the circuit: every argument of every slot, every other slot's multiplicity
-  std::vector<uint8_t> seen(c.nodes.size(), 0);
-  for (size_t j = 0; j < c.lookups.size(); j++) {
-    if (j != slot) dm_reach(c, c.lookups[j].first, seen);
-    for (uint32_t a : c.lookups[j].second) dm_reach(c, a, seen);
-  }
-  out3[0] = 0;
-  for (size_t k = 0; k < c.nodes.size(); k++)
-    if (seen[k] && c.nodes[k].kind == OP_VAR && c.nodes[k].source == 1 && c.nodes[k].a == var.a) out3[0] = 2;  // (at either offset)
-}
+// the classifier is host code over the node program alone (mult_slot.h), shared with the BabyBear configuration
+void multiplicity_slot(const HCircuit& c, size_t slot, u64 out3[3]) { multiplicity_slot(c.nodes, c.lookups, slot, out3); }
 
 void witness_derive_multiplicities(HSystem& sys, HWitness& wit, const ms_mult_target* targets, size_t n_targets, u64 summary[MS_DM_SUMMARY_WORDS],
                                    u64* entries, size_t entries_cap, u64* args_out, size_t args_cap) {
