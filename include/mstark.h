@@ -347,6 +347,57 @@ int32_t ms_witness_derive_multiplicities(ms_witness* w, const ms_mult_target* ta
                                          uint64_t summary[MS_DM_SUMMARY_WORDS], uint64_t* entries, size_t entries_cap /* nullable with cap 0 */,
                                          uint64_t* args_out, size_t args_cap /* nullable with cap 0 */);
 
+/* ---- Trace columns filled on the device from a program. ms_witness_derive_multiplicities produces the tables' multiplicity
+ * columns; this call produces the others - byte decompositions, carries, inverses, flags, padding - for one circuit of a
+ * witness whose traces are in HBM, from a FILL PROGRAM the caller authors in the front end (frontend.compile_fill) and,
+ * optionally, a matrix of inputs in device memory. Goldilocks / BLAKE3 configuration.
+ *   Program. A little-endian u64-word blob: a magic word (0x31304C4C49464D00), main_width, pre_width, n_inputs, n_nodes,
+ * n_steps; the nodes as [kind | source << 8 | offset << 16, a, b]; the steps as [dst, root]. Node kinds 0 (constant a), 1
+ * (variable a of source 0 preprocessed / 1 main / 3 input, at row offset 0 or 1), 6 add, 7 sub, 8 mul, 9 neg are those of the
+ * system blob; the witness-only kinds follow from 16: 16 row, 17 bits (b = lo | length << 8), 18 inv0, 19 lt, 20 xor, 21 and.
+ * Operands a, b of an operator are indices of EARLIER nodes. Stage-2 variables (source 2), publics (kind 2) and the three
+ * selector nodes (kinds 3-5) are refused: the selectors are polynomials here, not flags; flags come from row, lt and inv0.
+ *   Values at row r of a circuit of height n, operands taken as the canonical integers in [0, p):
+ *     input i at offset 0 / 1   column i of the input matrix at row r / row (r + 1) mod n; rows at or beyond its height read 0
+ *     preprocessed i            the circuit's preprocessed column at row r / row (r + 1) mod n
+ *     row                       r
+ *     add, sub, mul, neg        the field operations
+ *     bits(x, lo, length)       (x >> lo) & (2^length - 1), 1 <= length, lo + length <= 64
+ *     inv0(x)                   the inverse of x modulo p, and 0 for x = 0
+ *     lt(x, y)                  1 if x < y as integers, else 0
+ *     xor(x, y), and(x, y)      (x ^ y) mod p, x & y
+ *   Definition. The steps run in order for every row r: trace[r][dst_k] = the value of root_k at row r. A read of main column m
+ * at offset 0 sees the value of the latest EARLIER step of this call that assigned m, and what the trace held before the call
+ * if there is none. A read of main column m at offset 1 sees what row (r + 1) mod n held before the call and is allowed only if
+ * NO step of the program assigns m - that is what makes the row-parallel execution equal to this sequential definition. The
+ * same dst may appear in several steps; the last one wins. Every written value is canonical.
+ *   Held lookup values. Where the witness holds lookup values for the circuit they are recomputed by from_stage_1 on the device
+ * inside the same call, so that ms_prove, ms_stage2_build, ms_witness_check, ms_witness_lookup_balance and
+ * ms_witness_derive_multiplicities behind it see one consistent witness. Nothing else in the witness changes: other columns,
+ * other traces and the claims stay byte-identical.
+ *   inputs (nullable when the program has n_inputs = 0): one ms_dev_matrix as for ms_witness_create_device, of width n_inputs and
+ * a height in [0, n]; it is copied and checked by the same launch, and the library has finished reading it when the call
+ * returns, with any status. producer_stream orders that read behind the caller's stream exactly as there.
+ *   summary: [0] rows  [1] steps  [2] instructions executed per row (the linearised program: shared subexpressions once,
+ * nothing a later assignment overwrites unread)  [3] kernel form: lanes per workgroup with the slot file in LDS, 0 = slots in
+ * a global scratch walked in row batches.
+ *   MS_ERR (text via ms_last_error(); each refusal comes before anything is written, the context stays usable): a
+ * host-resident witness; a witness with circuits held by another rank; a circuit out of range or inactive; a blob with a wrong
+ * magic, a length that does not match its counts, widths other than the circuit's, a dst or a variable out of range, a forward
+ * operand, bad bits fields, a non-canonical constant or a refused node kind; an offset-1 read of an assigned column; an input
+ * matrix that fails the checks of ms_witness_create_device; an input height above n; n_inputs > 0 with inputs = NULL; an
+ * 8-byte input element >= p, naming the first offender in row-major order ("non-canonical input value: row 5, column 1"); a
+ * witness that holds lookup values for the circuit whose lookup prefix does not fit the device sweep.
+ *   Host waits: one when the program reads inputs of height > 0 (the offender word, before the first write); none otherwise -
+ * the call then only queues work on the context's stream. */
+int32_t ms_witness_fill(ms_witness* w, size_t circuit, const uint8_t* program, size_t program_len,
+                        const ms_dev_matrix* inputs /* nullable with n_inputs 0 */, void* producer_stream /* hipStream_t, nullable */,
+                        uint64_t summary[4]);
+/* Host code, no device: checks a fill program as ms_witness_fill does (everything that needs no witness) and describes how it
+ * would run: out4 = [instructions per row, live slots, lanes per workgroup of the LDS form (0: the slot file does not fit 64 KB
+ * at 64 lanes - global scratch), distinct assigned columns]. */
+int32_t ms_fill_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
+
 /* ---- System::prove_multiple_claims (src/prover.rs:290-603). Writes Proof::to_bytes (src/prover.rs:241-248).
  * stage_ms (optional, 6 doubles): stage1_commit, lookup_construction, stage2_commit, quotient, fri_open, total —
  * the reference's span names (src/prover.rs:336-538). Returns MS_ERR_BUFFER with *proof_len = needed size if

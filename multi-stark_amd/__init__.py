@@ -53,7 +53,7 @@ def exported_symbols():
             "ms_quotient_values", "ms_field_op", "ms_trace_destroy", "ms_trace_info", "ms_system_preprocessed_mmcs",
             "ms_witness_commit_stage1", "ms_challenger_observe_claims", "ms_witness_claims_accumulator", "ms_stage2_build",
             "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes", "ms_witness_check", "ms_system_check_info", "ms_witness_lookup_balance",
-            "ms_system_multiplicity_slot", "ms_witness_derive_multiplicities"]
+            "ms_system_multiplicity_slot", "ms_witness_derive_multiplicities", "ms_witness_fill", "ms_fill_program_info"]
 
 
 # ms_system_circuit_kernels / msbb_system_circuit_kernels (MS_KERNEL_* in include/mstark.h)
@@ -667,8 +667,59 @@ class MultiplicityReport:
         return "\n".join(out)
 
 
+def _program_bytes(program):
+    """the blob of a frontend.FillProgram, or the bytes themselves"""
+    blob = getattr(program, "blob", program)
+    return np.frombuffer(bytes(blob), dtype=np.uint8)
+
+
+def fill_program_info(program):
+    """ms_fill_program_info (host only): checks a fill program and tells how SystemWitness.fill would run it ->
+    {"instructions", "slots", "lds_lanes" (0: global scratch), "assigned_columns"}"""
+    a, o = _program_bytes(program), np.zeros(4, dtype=np.uint64)
+    _check(lib().ms_fill_program_info(_b(a), C.c_size_t(a.size), _p(o)))
+    return dict(zip(["instructions", "slots", "lds_lanes", "assigned_columns"], (int(x) for x in o)))
+
+
+class FillReport:
+    """What SystemWitness.fill returns: .rows, .steps, .instructions (executed per row), .lds_lanes (lanes per workgroup with the
+    slot file in LDS; 0: the slots lay in a global scratch)"""
+
+    def __init__(self, rows, steps, instructions, lds_lanes):
+        self.rows, self.steps, self.instructions, self.lds_lanes = rows, steps, instructions, lds_lanes
+
+    def fields(self):
+        return (self.rows, self.steps, self.instructions, self.lds_lanes)
+
+    def __str__(self):
+        form = "slots in LDS at %d lanes" % self.lds_lanes if self.lds_lanes else "slots in a global scratch"
+        return "%d rows x %d steps: %d instructions per row, %s" % (self.rows, self.steps, self.instructions, form)
+
+
 class SystemWitness:
     """Device-resident SystemWitness + claims (ms_witness). Built by `System.witness`."""
+
+    def fill(self, circuit, program, inputs=None, stream=None):
+        """ms_witness_fill: the columns of `circuit` that `program` (frontend.compile_fill, or its blob) assigns, evaluated on the
+        device for every row; held lookup values follow. inputs: None or a 2-D matrix in device memory (torch tensor or
+        __cuda_array_interface__; 1, 2, 4 or 8-byte elements read as unsigned; any strides) of at most the circuit's height,
+        rows beyond it read 0. stream: as for System.witness_from_device. -> FillReport"""
+        a = _program_bytes(program)
+        mat, seen = None, None
+        if inputs is not None:
+            ptr, shape, strides, item, is_torch = _device_array(inputs, "fill inputs")
+            if len(shape) != 2:
+                raise MstarkError("fill inputs: expected a 2-D matrix, got %d dimension(s)" % len(shape))
+            (h, w), (rs, cs) = shape, strides
+            want = int(a[24:32].view("<u8")[0]) if a.size >= 48 else w  # the blob's n_inputs word (a shorter blob is refused below)
+            if w != want:
+                raise MstarkError("fill inputs: width %d, the program reads %d input columns" % (w, want))
+            seen = inputs if is_torch else None
+            mat = DevMatrix(ptr or None, h, item, rs if h > 1 else max(w, 1), cs if w > 1 else 1)
+        summary = np.zeros(4, dtype=np.uint64)
+        _check(lib().ms_witness_fill(self.h, C.c_size_t(circuit), _b(a), C.c_size_t(a.size), C.byref(mat) if mat is not None else None,
+                                     _producer_stream(stream, seen), _p(summary)))
+        return FillReport(*(int(x) for x in summary))
 
     def derive_multiplicities(self, targets, entries=64):
         """ms_witness_derive_multiplicities: targets = [(circuit, lookup slot)], the provider slots whose multiplicity is one

@@ -405,6 +405,22 @@ int32_t ms_witness_derive_multiplicities(ms_witness* w, const ms_mult_target* ta
   return MS_OK;
   MS_CATCH
 }
+int32_t ms_witness_fill(ms_witness* w, size_t circuit, const uint8_t* program, size_t program_len, const ms_dev_matrix* inputs,
+                        void* producer_stream, uint64_t summary[4]) {
+  MS_TRY if (!w || !program || !summary) throw std::runtime_error("ms_witness_fill: null argument");
+  HWitness& wit = *w->w;
+  HSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  witness_fill(sys, wit, circuit, program, program_len, inputs, producer_stream, summary);
+  return MS_OK;
+  MS_CATCH
+}
+int32_t ms_fill_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]) {
+  MS_TRY if (!program || !out4) throw std::runtime_error("ms_fill_program_info: null argument");
+  fill_program_info(program, program_len, out4);
+  return MS_OK;
+  MS_CATCH
+}
 int32_t ms_system_check_info(const ms_system* sys, size_t ci, uint64_t out4[4]) {
   MS_TRY if (!sys || !out4) throw std::runtime_error("ms_system_check_info: null argument");
   const HSystem& s = *sys->sys;

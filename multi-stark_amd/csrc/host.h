@@ -232,6 +232,12 @@ size_t lookup_balance_slots(const HSystem& sys);  // sum of num_lookups over eve
 void witness_derive_multiplicities(HSystem& sys, HWitness& wit, const ms_mult_target* targets, size_t n_targets, u64 summary[MS_DM_SUMMARY_WORDS],
                                    u64* entries, size_t entries_cap, u64* args_out, size_t args_cap);
 void multiplicity_slot(const HCircuit& c, size_t slot, u64 out3[3]);  // ms_system_multiplicity_slot: [eligibility, column, pull]
+// ms_witness_fill (fill.hip): the columns a fill program assigns, evaluated for every row of circuit `ci` on the device; held
+// lookup values of the circuit follow. One host wait when the program reads inputs (their offender word), none otherwise
+void witness_fill(HSystem& sys, HWitness& wit, size_t ci, const uint8_t* program, size_t program_len, const ms_dev_matrix* inputs,
+                  void* producer_stream, u64 summary[4]);
+// ms_fill_program_info: host only - [instructions, live slots, lanes of the LDS form (0: global scratch), assigned columns]
+void fill_program_info(const uint8_t* program, size_t program_len, u64 out4[4]);
 void field_op(Ctx& ctx, int op, const u64* a, const u64* b, size_t n, u64* out);
 
 }  // namespace msamd

@@ -25,6 +25,10 @@ EXT_D, EXT_W = 2, 7  # Challenge = BinomialExtensionField<Goldilocks, 2>, X^2 = 
 N_CONST, N_VAR, N_PUBLIC, N_IS_FIRST, N_IS_LAST, N_IS_TRANS, N_ADD, N_SUB, N_MUL, N_NEG = range(10)
 SRC_PRE, SRC_MAIN, SRC_STAGE2 = 0, 1, 2
 BLOB_MAGIC = 0x31305359534D0000
+# witness-only node kinds and the input source of fill programs (compile_fill, ms_witness_fill): never part of a constraint
+N_ROW, N_BITS, N_INV0, N_LT, N_XOR, N_AND = range(16, 22)
+SRC_INPUT = 3
+FILL_MAGIC = 0x31304C4C49464D00
 
 # The two StarkGenericConfig instantiations of the reference: GoldilocksBlake3Config (src/types.rs:24-29,199-223) and
 # the BabyBear / degree-4 extension / Poseidon2 test configuration (src/test_circuits/baby_bear_config.rs:28-38).
@@ -77,6 +81,19 @@ class Expr:
     @staticmethod
     def public(i):
         return Expr(N_PUBLIC, int(i))
+
+    # witness-only leaves (fill programs)
+    @staticmethod
+    def input(i):
+        return Expr.var(SRC_INPUT, 0, i)
+
+    @staticmethod
+    def input_next(i):
+        return Expr.var(SRC_INPUT, 1, i)
+
+    @staticmethod
+    def row():
+        return Expr(N_ROW)
 
     def is_const(self, v=None):
         return self.kind == N_CONST and (v is None or self.a == v % P)
@@ -275,6 +292,8 @@ class _Interner:
 
     def compile_expr(self, e, spec, allow_stage2):
         k = e.kind
+        if k >= N_ROW or (k == N_VAR and e.source == SRC_INPUT):
+            raise CompileError("WitnessOnlyNode kind=%d: row, bits, inv0, lt, bit_xor, bit_and and inputs belong to fill programs" % k)
         if k == N_CONST:
             return self.constant(e.a)
         if k == N_VAR:
@@ -538,6 +557,150 @@ def system_blob(params, compiled, poseidon2=None):
             chunks.append(np.ascontiguousarray(pre, dtype=np.uint64).tobytes())
     chunks.append(np.asarray(words, dtype=np.uint64).tobytes())
     return b"".join(chunks)
+
+
+# --------------------------------------------------------------------------- fill programs (ms_witness_fill)
+# How the dependent columns of one circuit follow from inputs and other columns: an ordered list of steps (dst_column, Expr)
+# over the constraint algebra plus the witness-only leaves Expr.input / Expr.input_next / Expr.row and the operators below.
+# The semantics are written down in include/mstark.h; operands are the canonical integers in [0, P).
+def bits(x, lo, length):
+    """(x >> lo) & (2^length - 1), 1 <= length, lo + length <= 64"""
+    lo, length = int(lo), int(length)
+    if lo < 0 or length < 1 or lo + length > 64:
+        raise CompileError("BadBitsFields lo=%d length=%d" % (lo, length))
+    return Expr(N_BITS, Expr.lift(x), lo | (length << 8))
+
+
+def inv0(x):
+    """x^-1 mod P, and 0 for x = 0"""
+    return Expr(N_INV0, Expr.lift(x))
+
+
+def lt(x, y):
+    """1 if x < y as integers, else 0"""
+    return Expr(N_LT, Expr.lift(x), Expr.lift(y))
+
+
+def bit_xor(x, y):
+    """(x ^ y) mod P"""
+    return Expr(N_XOR, Expr.lift(x), Expr.lift(y))
+
+
+def bit_and(x, y):
+    """x & y"""
+    return Expr(N_AND, Expr.lift(x), Expr.lift(y))
+
+
+class _FillInterner(_Interner):
+    """The interner of compile_circuit with the witness-only nodes: equal subexpressions are shared, constants folded."""
+
+    def bits(self, a, f):
+        x = self.as_const(a)
+        if x is not None:
+            return self.constant((x >> (f & 0xFF)) & ((1 << (f >> 8)) - 1))
+        return self.intern((N_BITS, 0, 0, a, f))
+
+    def inv0(self, a):
+        x = self.as_const(a)
+        if x is not None:
+            return self.constant(pow(x, P - 2, P))
+        return self.intern((N_INV0, 0, 0, a, 0))
+
+    def lt(self, a, b):
+        x, y = self.as_const(a), self.as_const(b)
+        if x is not None and y is not None:
+            return self.constant(1 if x < y else 0)
+        return self.intern((N_LT, 0, 0, a, b))
+
+    def xor(self, a, b):
+        x, y = self.as_const(a), self.as_const(b)
+        if x is not None and y is not None:
+            return self.constant(x ^ y)
+        return self.intern((N_XOR, 0, 0, min(a, b), max(a, b)))
+
+    def and_(self, a, b):
+        x, y = self.as_const(a), self.as_const(b)
+        if x is not None and y is not None:
+            return self.constant(x & y)
+        return self.intern((N_AND, 0, 0, min(a, b), max(a, b)))
+
+    def compile_fill_expr(self, e, spec):
+        k = e.kind
+        if k == N_CONST:
+            return self.constant(e.a)
+        if k == N_VAR:
+            if e.source not in (SRC_PRE, SRC_MAIN, SRC_INPUT):
+                raise CompileError("Stage2InFillProgram")
+            width = {SRC_PRE: spec["preprocessed_width"], SRC_MAIN: spec["main_width"], SRC_INPUT: spec["n_inputs"]}[e.source]
+            if e.offset not in (0, 1):
+                raise CompileError("RowOffsetOutOfRange offset=%d" % e.offset)
+            if not 0 <= e.a < width:
+                raise CompileError("ColumnOutOfRange source=%d index=%d width=%d" % (e.source, e.a, width))
+            return self.intern((N_VAR, e.source, e.offset, e.a, 0))
+        if k in (N_PUBLIC, N_IS_FIRST, N_IS_LAST, N_IS_TRANS):
+            raise CompileError("NotAllowedInFillProgram kind=%d: publics and selector polynomials are no witness values "
+                               "(flags come from row, lt and inv0)" % k)
+        if k == N_ROW:
+            return self.intern((N_ROW, 0, 0, 0, 0))
+        if k not in (N_ADD, N_SUB, N_MUL, N_NEG, N_BITS, N_INV0, N_LT, N_XOR, N_AND):
+            raise CompileError("UnknownNodeKind kind=%d" % k)
+        a = self.compile_fill_expr(e.a, spec)
+        if k == N_NEG:
+            return self.neg(a)
+        if k == N_INV0:
+            return self.inv0(a)
+        if k == N_BITS:
+            return self.bits(a, e.b)
+        b = self.compile_fill_expr(e.b, spec)
+        return {N_ADD: self.add, N_SUB: self.sub, N_MUL: self.mul, N_LT: self.lt, N_XOR: self.xor, N_AND: self.and_}[k](a, b)
+
+
+def fill_blob(main_width, preprocessed_width, n_inputs, nodes, steps):
+    """The little-endian u64-word blob of a fill program, unchecked: magic, main_width, pre_width, n_inputs, n_nodes, n_steps,
+    the nodes as [kind | source << 8 | offset << 16, a, b], the steps as [dst, root]."""
+    words = [FILL_MAGIC, main_width, preprocessed_width, n_inputs, len(nodes), len(steps)]
+    for (kind, source, offset, a, b) in nodes:
+        words += [kind | (source << 8) | (offset << 16), a, b]
+    for (dst, root) in steps:
+        words += [dst, root]
+    return np.asarray(words, dtype=np.uint64).tobytes()
+
+
+class FillProgram:
+    """What compile_fill returns: .nodes (kind, source, offset, a, b), .steps (dst, root), the widths and .blob"""
+
+    def __init__(self, main_width, preprocessed_width, n_inputs, nodes, steps):
+        self.main_width, self.preprocessed_width, self.n_inputs = main_width, preprocessed_width, n_inputs
+        self.nodes, self.steps = nodes, steps
+        self.blob = fill_blob(main_width, preprocessed_width, n_inputs, nodes, steps)
+
+
+def compile_fill(main_width, preprocessed_width, n_inputs, steps):
+    """steps: [(dst_column, Expr)], run in order for every row (include/mstark.h, ms_witness_fill). -> FillProgram"""
+    spec = {"main_width": int(main_width), "preprocessed_width": int(preprocessed_width), "n_inputs": int(n_inputs)}
+    it = _FillInterner()
+    out = []
+    for k, (dst, e) in enumerate(steps):
+        dst = int(dst)
+        if not 0 <= dst < spec["main_width"]:
+            raise CompileError("DstOutOfRange step=%d dst=%d main_width=%d" % (k, dst, spec["main_width"]))
+        out.append((dst, it.compile_fill_expr(Expr.lift(e), spec)))
+    assigned = {dst for dst, _ in out}
+    for (kind, source, offset, a, _) in it.nodes:
+        if kind == N_VAR and source == SRC_MAIN and offset == 1 and a in assigned:
+            raise CompileError("NextRowOfAssignedColumn column=%d: a fill program may read the next row only of columns it does not assign" % a)
+    return FillProgram(spec["main_width"], spec["preprocessed_width"], spec["n_inputs"], it.nodes, out)
+
+
+def u32_add_fill_program(num_adds):
+    """The 14 columns of the U32Add circuit (u32_add_system_inputs) from inputs (x, y), one pair per row: the byte decompositions
+    of x, y and the low word of x + y, the carry, and the row's activity flag; rows from num_adds on come out as zeros."""
+    x, y = Expr.input(0), Expr.input(1)
+    s = x + y
+    steps = [(k, bits(x, 8 * k, 8)) for k in range(4)] + [(4 + k, bits(y, 8 * k, 8)) for k in range(4)]
+    steps += [(8 + k, bits(s, 8 * k, 8)) for k in range(4)]
+    steps += [(12, bits(s, 32, 1)), (13, lt(Expr.row(), num_adds))]
+    return compile_fill(14, 0, 2, steps)
 
 
 # --------------------------------------------------------------------------- circuits
