@@ -247,6 +247,9 @@ extern "C" {
     pub fn msbb_system_multiplicity_slot(sys: *const msbb_system, circuit: usize, slot: usize, out3: *mut u64) -> i32;
     pub fn msbb_witness_derive_multiplicities(w: *mut msbb_witness, targets: *const ms_mult_target, n_targets: usize, summary: *mut u64,
                                               entries: *mut u64, entries_cap: usize, args_out: *mut u32, args_cap: usize) -> i32;
+    pub fn msbb_witness_fill(w: *mut msbb_witness, circuit: usize, program: *const u8, program_len: usize, inputs: *const ms_dev_matrix,
+                             producer_stream: *mut c_void, summary: *mut u64) -> i32;
+    pub fn msbb_fill_program_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
     pub fn msbb_witness_trace(w: *mut msbb_witness, circuit: usize, out: *mut u32, cap_words: usize, n_words: *mut usize) -> i32;
     pub fn msbb_prove(sys: *mut msbb_system, w: *mut msbb_witness, proof_out: *mut u8, cap: usize, proof_len: *mut usize,
                       stage_ms: *mut f64) -> i32;

@@ -153,6 +153,47 @@ int32_t msbb_system_multiplicity_slot(const msbb_system* sys, size_t circuit, si
 int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target* targets, size_t n_targets,
                                            uint64_t summary[MS_DM_SUMMARY_WORDS], uint64_t* entries, size_t entries_cap /* nullable with cap 0 */,
                                            uint32_t* args_out, size_t args_cap /* nullable with cap 0; canonical values */);
+
+/* ---- Trace columns filled on the device from a program: ms_witness_fill (include/mstark.h, "Trace columns filled on the device")
+ * for this configuration, its definition read over p = 2^31 - 2^27 + 1, with the same notions: fill program, steps, the
+ * sequential definition (a read of an assigned column at offset 0 sees the latest earlier step; offset-1 reads only of columns no
+ * step assigns; the last assignment of a column wins), inputs and producer_stream. With msbb_witness_derive_multiplicities behind
+ * it the pipeline of the other configuration runs here too: fill, derive, check, prove, all in HBM. What differs from the
+ * Goldilocks call:
+ *   Blob: the same layout - u64 words, a header of six, nodes [kind | source << 8 | offset << 16, a, b], steps [dst, root] - under
+ * the magic word 0x3130424C49464D00 ("\0MFILB01"). The blob carries no other mark of its field and its constants were folded
+ * modulo the field it was authored over (frontend.compile_fill under frontend.field(BABYBEAR)), so each call refuses the other
+ * field's magic as a wrong magic instead of running the program with another meaning.
+ *   Values: operands are the canonical integers in [0, p). bits(x, lo, length) needs 1 <= length and lo + length <= 32;
+ * xor(x, y) = (x ^ y) mod p, one conditional subtraction as x ^ y < 2^31 < 2 p; and, lt, inv0 (0 -> 0) and row (r: heights are
+ * at most 2^27 < p) as there. A constant >= p is refused as non-canonical.
+ *   inputs: an ms_dev_matrix as for msbb_witness_create_device - elem_bytes 1, 2 or 4 - of width n_inputs and a height in
+ * [0, n]; rows at or beyond its height read 0. A 4-byte element >= p is refused, naming the first offender in row-major order
+ * ("non-canonical input value: row 5, column 1").
+ *   Storage: the library's copy of a trace, and of a preprocessed trace, is a column-major matrix of Montgomery words. The call
+ * reads and writes that form; every written cell is the Montgomery word of a canonical value, and msbb_witness_trace shows the
+ * canonical values.
+ *   No held lookup values: a witness of this configuration holds none, so nothing beside the assigned columns changes - other
+ * columns, other traces and the claims stay byte-identical - and every call behind this one sees the filled columns.
+ *   summary: [0] rows  [1] steps  [2] instructions executed per row  [3] kernel form: lanes per workgroup with the slot file in
+ * LDS (4-byte slots: 256 lanes up to 64 live slots, 128 up to 128, 64 up to 256), 0 = slots in a global scratch walked in row
+ * batches.
+ *   MS_ERR (text via ms_last_error(), starting "msbb_witness_fill: "; each refusal comes before anything is written, the context
+ * stays usable): the list of ms_witness_fill without its held-lookup case - a host-resident witness; a witness that does not
+ * belong to the system; a circuit out of range or inactive; a blob with a wrong magic, a length that does not match its counts,
+ * widths other than the circuit's, a dst or a variable out of range, a forward operand, bad bits fields, a non-canonical
+ * constant or a refused node kind; an offset-1 read of an assigned column; an input matrix that fails the checks of
+ * msbb_witness_create_device (8-byte elements among them); an input height above n; n_inputs > 0 with inputs = NULL; a
+ * non-canonical input element; a null w, program or summary.
+ *   Host waits: one when the program reads inputs of height > 0 (the offender word, before the first write); none otherwise. */
+int32_t msbb_witness_fill(msbb_witness* w, size_t circuit, const uint8_t* program, size_t program_len,
+                          const ms_dev_matrix* inputs /* nullable with n_inputs 0 */, void* producer_stream /* hipStream_t, nullable */,
+                          uint64_t summary[4]);
+/* Host code, no device: checks a fill program as msbb_witness_fill does (everything that needs no witness) and describes how it
+ * would run: out4 = [instructions per row, live slots, lanes per workgroup of the LDS form (0: global scratch), distinct assigned
+ * columns]. Texts start "msbb_fill_program_info: ". */
+int32_t msbb_fill_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
+
 /* Diagnostics, as ms_witness_trace: one stage-1 trace of a device-resident witness read back, height x main_width, row-major,
  * canonical u32. MS_ERR_BUFFER with *n_words = the needed size; an inactive circuit: 0 words, MS_OK. A host-resident witness or
  * an out-of-range circuit: MS_ERR. */

@@ -24,7 +24,8 @@ def exported_symbols():
             "msbb_challenger_sample_ext", "msbb_challenger_sample_bits", "msbb_challenger_observe_claims", "msbb_trace_destroy", "msbb_trace_info",
             "msbb_system_preprocessed_mmcs", "msbb_witness_commit_stage1", "msbb_witness_claims_accumulator", "msbb_stage2_build",
             "msbb_pcs_commit_traces", "msbb_quotient", "msbb_pcs_commit_ldes", "msbb_pcs_open", "msbb_witness_check", "msbb_system_check_info",
-            "msbb_witness_lookup_balance", "msbb_system_multiplicity_slot", "msbb_witness_derive_multiplicities", "msbb_witness_trace"]
+            "msbb_witness_lookup_balance", "msbb_system_multiplicity_slot", "msbb_witness_derive_multiplicities", "msbb_witness_trace",
+            "msbb_witness_fill", "msbb_fill_program_info"]
 
 
 import sys
@@ -72,7 +73,38 @@ CHECK_GAMMA = tuple(x % P for x in (0xA4093822, 0x299F31D0, 0x082EFA98, 0xEC4E6C
 CHECK_CIRCUIT_WORDS = 12  # MSBB_CHECK_CIRCUIT_WORDS of include/mstark_bb.h
 
 
+def fill_program_info(program):
+    """msbb_fill_program_info (host only): checks a fill program compiled under frontend.field(BABYBEAR) and tells how
+    Witness.fill would run it -> {"instructions", "slots", "lds_lanes" (0: global scratch), "assigned_columns"}"""
+    a, o = _pkg()._program_bytes(program), np.zeros(4, dtype=np.uint64)
+    _check(_lib().msbb_fill_program_info(a.ctypes.data_as(u8p), C.c_size_t(a.size), o.ctypes.data_as(u64p)))
+    return dict(zip(["instructions", "slots", "lds_lanes", "assigned_columns"], (int(x) for x in o)))
+
+
 class Witness:
+    def fill(self, circuit, program, inputs=None, stream=None):
+        """msbb_witness_fill: the columns of `circuit` that `program` (frontend.compile_fill under field(BABYBEAR), or its blob)
+        assigns, evaluated on the device for every row. inputs: None or a 2-D matrix in device memory (torch tensor or
+        __cuda_array_interface__; 1, 2 or 4-byte elements read as unsigned canonical values; any strides) of at most the
+        circuit's height, rows beyond it read 0. stream: as for System.witness_from_device. -> the package's FillReport"""
+        pkg = _pkg()
+        a = pkg._program_bytes(program)
+        mat, seen = None, None
+        if inputs is not None:
+            ptr, shape, strides, item, is_torch = pkg._device_array(inputs, "fill inputs")
+            if len(shape) != 2:
+                raise pkg.MstarkError("fill inputs: expected a 2-D matrix, got %d dimension(s)" % len(shape))
+            (h, w), (rs, cs) = shape, strides
+            want = int(a[24:32].view("<u8")[0]) if a.size >= 48 else w  # the blob's n_inputs word (a shorter blob is refused below)
+            if w != want:
+                raise pkg.MstarkError("fill inputs: width %d, the program reads %d input columns" % (w, want))
+            seen = inputs if is_torch else None
+            mat = pkg.DevMatrix(ptr or None, h, item, rs if h > 1 else max(w, 1), cs if w > 1 else 1)
+        summary = np.zeros(4, dtype=np.uint64)
+        _check(_lib().msbb_witness_fill(self.h, C.c_size_t(circuit), a.ctypes.data_as(u8p), C.c_size_t(a.size),
+                                        C.byref(mat) if mat is not None else None, pkg._producer_stream(stream, seen), summary.ctypes.data_as(u64p)))
+        return pkg.FillReport(*(int(x) for x in summary))
+
     def check(self, beta=None, gamma=None, names=None, origins=None):
         """msbb_witness_check: every user constraint root of every active circuit on the trace domain, and the lookup balance
         under (beta, gamma) - four canonical coordinates each, default CHECK_BETA / CHECK_GAMMA. -> the package's CheckReport

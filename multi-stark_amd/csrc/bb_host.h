@@ -194,6 +194,11 @@ void witness_lookup_balance(BSystem& sys, BWitness& wit, u64 summary[4], u64* en
 void witness_derive_multiplicities(BSystem& sys, BWitness& wit, const ms_mult_target* targets, size_t n_targets, u64 summary[MS_DM_SUMMARY_WORDS],
                                    u64* entries, size_t entries_cap, u32* args_out, size_t args_cap);
 void multiplicity_slot(const BCircuit& c, size_t slot, u64 out3[3]);  // msbb_system_multiplicity_slot: [eligibility, column, pull]
+// msbb_witness_fill (bb_fill.hip): the columns of one circuit that a fill program assigns, evaluated for every row of the
+// column-major Montgomery trace; inputs nullable when the program reads none. One host wait when inputs are read, none otherwise
+void witness_fill(BSystem& sys, BWitness& wit, size_t circuit, const uint8_t* program, size_t program_len, const ms_dev_matrix* inputs,
+                  void* producer_stream, u64 summary[4]);
+void fill_program_info(const uint8_t* program, size_t program_len, u64 out4[4]);  // host only: [instructions, slots, LDS lanes, assigned columns]
 // MerkleTreeMmcs::verify_batch for many openings of one commitment, one device thread per opening; everything canonical
 void mmcs_verify_batch_device(Ctx& ctx, const Poseidon2* d_perm, const std::vector<size_t>& heights, const std::vector<size_t>& widths,
                               const u32* cap, unsigned cap_height, size_t n_openings, const u64* indices, const u32* vals, const u32* siblings,

@@ -1566,6 +1566,24 @@ int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target
   return MS_OK;
   BB_CATCH
 }
+int32_t msbb_witness_fill(msbb_witness* w, size_t circuit, const uint8_t* program, size_t program_len, const ms_dev_matrix* inputs,
+                          void* producer_stream, uint64_t summary[4]) {
+  BB_TRY
+  if (!w || !program || !summary) throw std::runtime_error("msbb_witness_fill: null argument");
+  BWitness& wit = *w->w;
+  BSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  witness_fill(sys, wit, circuit, program, program_len, inputs, producer_stream, summary);
+  return MS_OK;
+  BB_CATCH
+}
+int32_t msbb_fill_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]) {
+  BB_TRY
+  if (!program || !out4) throw std::runtime_error("msbb_fill_program_info: null argument");
+  fill_program_info(program, program_len, out4);
+  return MS_OK;
+  BB_CATCH
+}
 int32_t msbb_witness_trace(msbb_witness* w, size_t circuit, uint32_t* out, size_t cap_words, size_t* n_words) {
   BB_TRY
   if (!w || !n_words) throw std::runtime_error("msbb_witness_trace: null argument");

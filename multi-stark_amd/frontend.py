@@ -28,12 +28,14 @@ BLOB_MAGIC = 0x31305359534D0000
 # witness-only node kinds and the input source of fill programs (compile_fill, ms_witness_fill): never part of a constraint
 N_ROW, N_BITS, N_INV0, N_LT, N_XOR, N_AND = range(16, 22)
 SRC_INPUT = 3
-FILL_MAGIC = 0x31304C4C49464D00
+FILL_MAGIC = 0x31304C4C49464D00  # "\0MFILL01"; over BabyBear "\0MFILB01": a fill program belongs to the field its constants were folded in
+FILL_BITS = 64  # bits(x, lo, length) needs lo + length <= the width of a value: 64, over BabyBear 32
 
 # The two StarkGenericConfig instantiations of the reference: GoldilocksBlake3Config (src/types.rs:24-29,199-223) and
 # the BabyBear / degree-4 extension / Poseidon2 test configuration (src/test_circuits/baby_bear_config.rs:28-38).
-GOLDILOCKS = dict(name="goldilocks", P=P, EXT_D=2, EXT_W=7, BLOB_MAGIC=0x31305359534D0000)
-BABYBEAR = dict(name="babybear", P=(1 << 31) - (1 << 27) + 1, EXT_D=4, EXT_W=11, BLOB_MAGIC=0x31304259534D0000)
+GOLDILOCKS = dict(name="goldilocks", P=P, EXT_D=2, EXT_W=7, BLOB_MAGIC=0x31305359534D0000, FILL_MAGIC=0x31304C4C49464D00, FILL_BITS=64)
+BABYBEAR = dict(name="babybear", P=(1 << 31) - (1 << 27) + 1, EXT_D=4, EXT_W=11, BLOB_MAGIC=0x31304259534D0000, FILL_MAGIC=0x3130424C49464D00,
+                FILL_BITS=32)
 
 
 @contextlib.contextmanager
@@ -41,7 +43,7 @@ def field(cfg):
     """Author circuits / witnesses / blobs over another configuration's field: `with frontend.field(frontend.BABYBEAR):`.
     (The reference picks the field through the SC type parameter; this front-end keeps it in module state.)"""
     g = globals()
-    saved = {k: g[k] for k in ("P", "EXT_D", "EXT_W", "BLOB_MAGIC")}
+    saved = {k: g[k] for k in ("P", "EXT_D", "EXT_W", "BLOB_MAGIC", "FILL_MAGIC", "FILL_BITS")}
     g.update({k: cfg[k] for k in saved})
     try:
         yield cfg
@@ -564,9 +566,9 @@ def system_blob(params, compiled, poseidon2=None):
 # over the constraint algebra plus the witness-only leaves Expr.input / Expr.input_next / Expr.row and the operators below.
 # The semantics are written down in include/mstark.h; operands are the canonical integers in [0, P).
 def bits(x, lo, length):
-    """(x >> lo) & (2^length - 1), 1 <= length, lo + length <= 64"""
+    """(x >> lo) & (2^length - 1), 1 <= length, lo + length <= 64 (32 under field(BABYBEAR))"""
     lo, length = int(lo), int(length)
-    if lo < 0 or length < 1 or lo + length > 64:
+    if lo < 0 or length < 1 or lo + length > FILL_BITS:
         raise CompileError("BadBitsFields lo=%d length=%d" % (lo, length))
     return Expr(N_BITS, Expr.lift(x), lo | (length << 8))
 
@@ -701,6 +703,21 @@ def u32_add_fill_program(num_adds):
     steps += [(8 + k, bits(s, 8 * k, 8)) for k in range(4)]
     steps += [(12, bits(s, 32, 1)), (13, lt(Expr.row(), num_adds))]
     return compile_fill(14, 0, 2, steps)
+
+
+def u32_add_halves_fill_program(num_adds):
+    """The 14 columns of the U32Add circuit from inputs (x_lo, x_hi, y_lo, y_hi), the 16-bit halves of one pair per row. No
+    intermediate value reaches 2^18, so the program means the same over both fields (u32_add_fill_program reads bit 32 of x + y,
+    which a field below 2^31 cannot hold): s_lo = x_lo + y_lo, s_hi = x_hi + y_hi + its carry, the bytes of the six halves, the
+    carry of s_hi, and the row's activity flag; rows from num_adds on come out as zeros."""
+    x_lo, x_hi, y_lo, y_hi = (Expr.input(k) for k in range(4))
+    s_lo = x_lo + y_lo
+    s_hi = x_hi + y_hi + bits(s_lo, 16, 1)
+    steps = []
+    for base, (lo, hi) in ((0, (x_lo, x_hi)), (4, (y_lo, y_hi)), (8, (s_lo, s_hi))):
+        steps += [(base, bits(lo, 0, 8)), (base + 1, bits(lo, 8, 8)), (base + 2, bits(hi, 0, 8)), (base + 3, bits(hi, 8, 8))]
+    steps += [(12, bits(s_hi, 16, 1)), (13, lt(Expr.row(), num_adds))]
+    return compile_fill(14, 0, 4, steps)
 
 
 # --------------------------------------------------------------------------- circuits
