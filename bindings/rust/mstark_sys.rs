@@ -208,6 +208,7 @@ extern "C" {
     pub fn ms_witness_fill(w: *mut ms_witness, circuit: usize, program: *const u8, program_len: usize, inputs: *const ms_dev_matrix,
                            producer_stream: *mut c_void, summary: *mut u64) -> i32;
     pub fn ms_fill_program_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
+    pub fn ms_fill_scan_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
     pub fn ms_witness_claims_accumulator(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_out: *mut u64) -> i32;
     pub fn ms_stage2_build(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_in: *const u64, accs_out: *mut u64,
                            traces_out: *mut *mut ms_trace) -> i32;

@@ -389,14 +389,49 @@ int32_t ms_witness_derive_multiplicities(ms_witness* w, const ms_mult_target* ta
  * 8-byte input element >= p, naming the first offender in row-major order ("non-canonical input value: row 5, column 1"); a
  * witness that holds lookup values for the circuit whose lookup prefix does not fit the device sweep.
  *   Host waits: one when the program reads inputs of height > 0 (the offender word, before the first write); none otherwise -
- * the call then only queues work on the context's stream. */
+ * the call then only queues work on the context's stream.
+ *
+ *   SCAN STEPS: columns that follow the previous row (running sums and products, counters, Horner accumulators). A step is
+ * ORDINARY, (dst, root) as above, or a SCAN (dst, mul root A, add root B, init). The definition is column at a time: step k
+ * computes its whole column before step k + 1 starts - for ordinary steps that equals the definition above. A scan step writes
+ *     trace[0][dst]     = init
+ *     trace[r + 1][dst] = A(r) * trace[r][dst] + B(r)  (mod p),  r = 0 .. n - 2
+ * where A(r), B(r) are the values the roots would have at row r if an ordinary step stood at that position. A(n - 1) and
+ * B(n - 1) are not used: there is no wrap-around, as under is_transition; at n = 1 only init is written. Every written value
+ * is canonical. The affine maps x -> A x + B compose associatively and exactly, so the device's parallel scan is bit-identical
+ * to this loop.
+ *   Groups. Each scan step is a group of its own; each maximal run of ordinary steps between scans is a group. Inside a group
+ * the rules above hold (an offset-0 read of an assigned column sees the latest earlier step of the group, shared subexpressions
+ * are computed once, each cell is stored once per group); a read of a column that an earlier group assigned comes from the
+ * trace. A read of main column m at offset 1 by a step of group g is allowed exactly when no step of group g or of any later
+ * group assigns m - with one group this is the rule above - so a later step may read the next row of a finished scan column
+ * (diff = s_next - s; at row n - 1 that is row 0). The coefficients of a scan step may not read its own dst at either offset.
+ *   Blob. A program without a scan step is the blob above. With scans: the magic word 0x32304C4C49464D00 ("\0MFILL02"), then
+ * main_width, pre_width, n_inputs, n_nodes, n_steps, n_scans (seven header words with the magic); the nodes; the steps as
+ * [dst, root], root of a scan step being its add root B; n_scans records [step index, mul root, init] with strictly ascending
+ * step indices. Nodes that no step reaches are not subject to the offset-1 rule in this format.
+ *   Execution: the groups in order on the context's stream - an ordinary group as above, a scan group as a coefficient pass
+ * (the same kernel, writing A and B into a temporary) and a three-launch scan over tiles of T rows (ms_fill_scan_info tells T);
+ * a mul root that is the constant 1 takes the additive form (B alone, no multiplications). Temporaries: 16 bytes x n for the
+ * call (8 when every scan is additive), shared by its scans, plus 24 bytes per tile. Held lookup values are recomputed once, at
+ * the end. Host waits are unchanged. summary for such a program: [1] all steps, [2] instructions per row summed over every
+ * launch of the fill kernel, coefficient passes included, [3] the smallest lanes figure over those launches (0 if any of
+ * them uses the global scratch).
+ *   MS_ERR in addition, before anything is written: a length that does not match the three counts; a scan record whose step
+ * index is out of range or not above the one before, whose mul root is out of range or whose init is >= p; a scan step whose
+ * coefficients read its own dst; an offset-1 read that the group rule refuses. msbb_witness_fill refuses the blob by its magic. */
 int32_t ms_witness_fill(ms_witness* w, size_t circuit, const uint8_t* program, size_t program_len,
                         const ms_dev_matrix* inputs /* nullable with n_inputs 0 */, void* producer_stream /* hipStream_t, nullable */,
                         uint64_t summary[4]);
 /* Host code, no device: checks a fill program as ms_witness_fill does (everything that needs no witness) and describes how it
  * would run: out4 = [instructions per row, live slots, lanes per workgroup of the LDS form (0: the slot file does not fit 64 KB
- * at 64 lanes - global scratch), distinct assigned columns]. */
+ * at 64 lanes - global scratch), distinct assigned columns]. For a program with scan steps: instructions summed over the
+ * launches of the fill kernel, the largest slot count and the smallest lanes figure among them, and the dst columns of scan
+ * steps count as assigned. */
 int32_t ms_fill_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
+/* Host code, no device: the same checks, and out4 = [scan steps, launches of the fill kernel (one per group of ordinary steps,
+ * one coefficient pass per scan), scans in the additive form, T = rows per scan tile]. Texts start "ms_fill_scan_info: ". */
+int32_t ms_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
 
 /* ---- System::prove_multiple_claims (src/prover.rs:290-603). Writes Proof::to_bytes (src/prover.rs:241-248).
  * stage_ms (optional, 6 doubles): stage1_commit, lookup_construction, stage2_commit, quotient, fri_open, total —

@@ -53,7 +53,8 @@ def exported_symbols():
             "ms_quotient_values", "ms_field_op", "ms_trace_destroy", "ms_trace_info", "ms_system_preprocessed_mmcs",
             "ms_witness_commit_stage1", "ms_challenger_observe_claims", "ms_witness_claims_accumulator", "ms_stage2_build",
             "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes", "ms_witness_check", "ms_system_check_info", "ms_witness_lookup_balance",
-            "ms_system_multiplicity_slot", "ms_witness_derive_multiplicities", "ms_witness_fill", "ms_fill_program_info"]
+            "ms_system_multiplicity_slot", "ms_witness_derive_multiplicities", "ms_witness_fill", "ms_fill_program_info",
+            "ms_fill_scan_info"]
 
 
 # ms_system_circuit_kernels / msbb_system_circuit_kernels (MS_KERNEL_* in include/mstark.h)
@@ -681,6 +682,14 @@ def fill_program_info(program):
     return dict(zip(["instructions", "slots", "lds_lanes", "assigned_columns"], (int(x) for x in o)))
 
 
+def fill_scan_info(program):
+    """ms_fill_scan_info (host only): checks a fill program and tells its scan steps -> (scan steps, launches of the fill kernel
+    (one per group of ordinary steps, one coefficient pass per scan), scans in the additive form, T = rows per scan tile)"""
+    a, o = _program_bytes(program), np.zeros(4, dtype=np.uint64)
+    _check(lib().ms_fill_scan_info(_b(a), C.c_size_t(a.size), _p(o)))
+    return tuple(int(x) for x in o)
+
+
 class FillReport:
     """What SystemWitness.fill returns: .rows, .steps, .instructions (executed per row), .lds_lanes (lanes per workgroup with the
     slot file in LDS; 0: the slots lay in a global scratch)"""
@@ -703,7 +712,9 @@ class SystemWitness:
         """ms_witness_fill: the columns of `circuit` that `program` (frontend.compile_fill, or its blob) assigns, evaluated on the
         device for every row; held lookup values follow. inputs: None or a 2-D matrix in device memory (torch tensor or
         __cuda_array_interface__; 1, 2, 4 or 8-byte elements read as unsigned; any strides) of at most the circuit's height,
-        rows beyond it read 0. stream: as for System.witness_from_device. -> FillReport"""
+        rows beyond it read 0. stream: as for System.witness_from_device. A program with scan steps (frontend.scan) runs in the
+        same call, group by group; its report sums the instructions and gives the smallest lanes figure over the launches of
+        the fill kernel. -> FillReport"""
         a = _program_bytes(program)
         mat, seen = None, None
         if inputs is not None:

@@ -421,6 +421,12 @@ int32_t ms_fill_program_info(const uint8_t* program, size_t program_len, uint64_
   return MS_OK;
   MS_CATCH
 }
+int32_t ms_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t out4[4]) {
+  MS_TRY if (!program || !out4) throw std::runtime_error("ms_fill_scan_info: null argument");
+  fill_scan_info(program, program_len, out4);
+  return MS_OK;
+  MS_CATCH
+}
 int32_t ms_system_check_info(const ms_system* sys, size_t ci, uint64_t out4[4]) {
   MS_TRY if (!sys || !out4) throw std::runtime_error("ms_system_check_info: null argument");
   const HSystem& s = *sys->sys;

@@ -15,6 +15,22 @@
 // Order on the context's stream: program upload, [wait for the producer's stream, ingest of the inputs into a row-major
 // temporary with the offender word, ONE host wait for that word], fill_k, lookup_values_k when the witness holds lookup values
 // for the circuit. Every refusal comes before fill_k is launched.
+//
+// SCAN steps (a program of the second format): trace[0][dst] = init, trace[r+1][dst] = A(r) * trace[r][dst] + B(r). The groups
+// of the program run in order on the stream: an ordinary group is one fill_k launch as above; a scan group is its COEFFICIENT
+// PASS - fill_k over the roots A, B with an n x 2 row-major temporary as its output (16 bytes per row; n x 1, B alone, when A is
+// the constant 1: the ADDITIVE form, no multiplications) - and then the scan of the affine maps x -> a x + b, whose composition
+// is associative and exact, so the parallel result equals the sequential loop bit for bit. Row r carries the map (A(r-1), B(r-1)),
+// row 0 the map (1, init), and the value before row 0 is 0. A tile is FL_SCAN_TILE = 256 threads x 4 consecutive rows:
+//   (a) scan_reduce_k   one workgroup per tile composes its rows into one aggregate: a thread composes its 4 rows, a wave scans
+//                       the 64 thread aggregates with shuffles, the 4 wave aggregates are joined through LDS
+//   (b) scan_starts_k   ONE workgroup turns the tile aggregates into the value in front of each tile, 256 aggregates per round
+//                       with the value behind the round carried into the next
+//   (c) scan_apply_k    one workgroup per tile scans its rows again from that value and stores the dst cells, each once
+// and a circuit of at most one tile takes launch (c) alone. No workgroup waits for another inside a kernel: the three phases are
+// ordered by the launches. Bytes per row and scan: 16 written by the coefficient pass, 16 read by (a), 16 read and 8 written by
+// (c) - 56 (additive: 8 + 8 + 8 + 8 = 32), next to what the pass itself reads; (a) and (b) move 24 / 1024 bytes per row more.
+// Temporaries of the call: 16 bytes x n (8 when every scan is additive), shared by its scans, and 24 bytes per tile.
 #include <algorithm>
 
 #include "fill_program.h"
@@ -28,7 +44,9 @@ namespace {
 constexpr const char* FL_CALL = "ms_witness_fill";
 
 struct FlParams {
-  u64* trace;                 // n x main_w row-major, read and written
+  const u64* trace;           // n x main_w row-major, read
+  u64* out;                   // n x out_w row-major, written: the trace (out_w = main_w), or the temporary of a coefficient pass
+  uint32_t out_w;
   const u64 *pre, *inp;       // n x pre_w and h_in x n_in, row-major
   size_t n, h_in;
   uint32_t main_w, pre_w, n_in;
@@ -86,14 +104,149 @@ __global__ __launch_bounds__(256) void fill_k(FlParams p) {
     }
     slots[ins.y * stride] = v;
   }
-  for (u32 o = 0; o < p.n_outs; o++) p.trace[r * p.main_w + p.outs[2 * o]] = slots[p.outs[2 * o + 1] * stride];
+  for (u32 o = 0; o < p.n_outs; o++) p.out[r * p.out_w + p.outs[2 * o]] = slots[p.outs[2 * o + 1] * stride];
+}
+
+// ---- scan steps: the affine map x -> a x + b (ADD: a = 1 throughout and is not carried)
+constexpr u32 SC_THREADS = 256, SC_ROWS = 4, SC_TILE = SC_THREADS * SC_ROWS, SC_WAVES = SC_THREADS / 64;
+
+struct Aff {
+  u64 a, b;
+};
+
+struct ScParams {
+  u64* trace;      // n x main_w row-major; column dst is written
+  const u64* tmp;  // the coefficient pass's output: n x 2 (A, B), ADD: n x 1 (B)
+  u64* aggs;       // per tile: (a, b), ADD: b
+  u64* starts;     // per tile: the value in front of its first row (nullptr: one tile, 0)
+  size_t n;
+  u64 init;
+  uint32_t main_w, dst, n_tiles;
+};
+
+template <bool ADD>
+__device__ __forceinline__ Aff sc_then(Aff f, Aff g) {  // f first, then g
+  if (ADD) return Aff{1, gl_add(f.b, g.b)};
+  return Aff{gl_mul(g.a, f.a), gl_add(gl_mul(g.a, f.b), g.b)};
+}
+template <bool ADD>
+__device__ __forceinline__ u64 sc_at(Aff f, u64 x) {
+  return ADD ? gl_add(x, f.b) : gl_add(gl_mul(f.a, x), f.b);
+}
+__device__ __forceinline__ u64 sc_up(u64 v, u32 d) { return (u64)__shfl_up((unsigned long long)v, d, 64); }
+
+// the map of row r: (1, init) at row 0, (A(r-1), B(r-1)) behind it, the identity from row n on
+template <bool ADD>
+__device__ __forceinline__ Aff sc_row(const ScParams& p, size_t r) {
+  if (r >= p.n) return Aff{1, 0};
+  if (r == 0) return Aff{1, p.init};
+  if (ADD) return Aff{1, p.tmp[r - 1]};
+  const ulonglong2 v = reinterpret_cast<const ulonglong2*>(p.tmp)[r - 1];
+  return Aff{v.x, v.y};
+}
+
+// Every thread of the workgroup brings the map of its rows (threads in row order): excl = the maps of all earlier threads
+// composed, total = those of the whole workgroup. sm: SC_WAVES entries; free again on return.
+template <bool ADD>
+__device__ __forceinline__ void sc_block_scan(Aff mine, Aff& excl, Aff& total, Aff* sm) {
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Aff inc = mine;
+  for (u32 d = 1; d < 64; d <<= 1) {
+    Aff prev{ADD ? 1 : sc_up(inc.a, d), sc_up(inc.b, d)};  // (every lane takes part in the shuffle)
+    if (lane >= d) inc = sc_then<ADD>(prev, inc);
+  }
+  if (lane == 63) sm[wave] = inc;
+  Aff pre{ADD ? 1 : sc_up(inc.a, 1), sc_up(inc.b, 1)};
+  if (lane == 0) pre = Aff{1, 0};
+  __syncthreads();
+  Aff before{1, 0};
+  total = Aff{1, 0};
+  for (u32 k = 0; k < SC_WAVES; k++) {
+    const Aff w = sm[k];
+    if (k < wave) before = sc_then<ADD>(before, w);
+    total = sc_then<ADD>(total, w);
+  }
+  excl = sc_then<ADD>(before, pre);
+  __syncthreads();
+}
+
+template <bool ADD>
+__global__ __launch_bounds__(SC_THREADS) void scan_reduce_k(ScParams p) {
+  __shared__ Aff sm[SC_WAVES];
+  const size_t r0 = blockIdx.x * size_t(SC_TILE) + threadIdx.x * SC_ROWS;
+  Aff mine = sc_row<ADD>(p, r0);
+  for (u32 j = 1; j < SC_ROWS; j++) mine = sc_then<ADD>(mine, sc_row<ADD>(p, r0 + j));
+  Aff excl, total;
+  sc_block_scan<ADD>(mine, excl, total, sm);
+  if (threadIdx.x == 0) {
+    if (ADD) {
+      p.aggs[blockIdx.x] = total.b;
+    } else {
+      p.aggs[2 * size_t(blockIdx.x)] = total.a;
+      p.aggs[2 * size_t(blockIdx.x) + 1] = total.b;
+    }
+  }
+}
+
+template <bool ADD>
+__global__ __launch_bounds__(SC_THREADS) void scan_starts_k(ScParams p) {  // one workgroup
+  __shared__ Aff sm[SC_WAVES];
+  u64 carry = 0;  // the value in front of the round's first tile
+  for (u32 t0 = 0; t0 < p.n_tiles; t0 += SC_THREADS) {
+    const u32 t = t0 + threadIdx.x;
+    Aff mine{1, 0};
+    if (t < p.n_tiles) mine = ADD ? Aff{1, p.aggs[t]} : Aff{p.aggs[2 * size_t(t)], p.aggs[2 * size_t(t) + 1]};
+    Aff excl, total;
+    sc_block_scan<ADD>(mine, excl, total, sm);
+    if (t < p.n_tiles) p.starts[t] = sc_at<ADD>(excl, carry);
+    carry = sc_at<ADD>(total, carry);
+  }
+}
+
+template <bool ADD>
+__global__ __launch_bounds__(SC_THREADS) void scan_apply_k(ScParams p) {
+  __shared__ Aff sm[SC_WAVES];
+  const size_t r0 = blockIdx.x * size_t(SC_TILE) + threadIdx.x * SC_ROWS;
+  Aff row[SC_ROWS];
+  for (u32 j = 0; j < SC_ROWS; j++) row[j] = sc_row<ADD>(p, r0 + j);
+  Aff mine = row[0];
+  for (u32 j = 1; j < SC_ROWS; j++) mine = sc_then<ADD>(mine, row[j]);
+  Aff excl, total;
+  sc_block_scan<ADD>(mine, excl, total, sm);
+  u64 x = sc_at<ADD>(excl, p.starts ? p.starts[blockIdx.x] : 0);
+  for (u32 j = 0; j < SC_ROWS; j++) {
+    x = sc_at<ADD>(row[j], x);
+    if (r0 + j < p.n) p.trace[(r0 + j) * p.main_w + p.dst] = x;
+  }
+}
+
+template <bool ADD>
+void scan_launch(Ctx& ctx, const ScParams& p) {
+  if (p.n_tiles > 1) {
+    hipLaunchKernelGGL(scan_reduce_k<ADD>, dim3(p.n_tiles), dim3(SC_THREADS), 0, ctx.stream, p);
+    hipLaunchKernelGGL(scan_starts_k<ADD>, dim3(1), dim3(SC_THREADS), 0, ctx.stream, p);
+  }
+  hipLaunchKernelGGL(scan_apply_k<ADD>, dim3(p.n_tiles), dim3(SC_THREADS), 0, ctx.stream, p);
+}
+
+unsigned fl_min_lanes(const FillCode& fc) {
+  unsigned lanes = 256;
+  for (const FillGroup& g : fc.groups) lanes = std::min(lanes, fill_lds_lanes(g.pass.n_slots, 8));
+  return lanes;
 }
 
 }  // namespace
 
 void fill_program_info(const uint8_t* program, size_t program_len, u64 out4[4]) {
   const FillCode fc = fill_compile(program, program_len, "ms_fill_program_info", FILL_GOLDILOCKS);
-  out4[0] = fc.n_instr, out4[1] = fc.n_slots, out4[2] = fill_lds_lanes(fc.n_slots, 8), out4[3] = fc.n_assigned;
+  out4[0] = fc.n_instr, out4[1] = fc.n_slots, out4[2] = fl_min_lanes(fc), out4[3] = fc.n_assigned;
+}
+
+void fill_scan_info(const uint8_t* program, size_t program_len, u64 out4[4]) {
+  const FillCode fc = fill_compile(program, program_len, "ms_fill_scan_info", FILL_GOLDILOCKS);
+  size_t launches = 0;
+  for (const FillGroup& g : fc.groups) launches += !g.pass.outs.empty();
+  out4[0] = fc.n_scans, out4[1] = launches, out4[2] = fc.n_additive, out4[3] = SC_TILE;
 }
 
 void witness_fill(HSystem& sys, HWitness& wit, size_t ci, const uint8_t* program, size_t program_len, const ms_dev_matrix* inputs,
@@ -133,21 +286,48 @@ void witness_fill(HSystem& sys, HWitness& wit, size_t ci, const uint8_t* program
       }
     }
   }
-  const unsigned lanes = fill_lds_lanes(fc.n_slots, 8);
-  summary[0] = n, summary[1] = fc.n_steps, summary[2] = fc.n_instr, summary[3] = lanes;
-  if (fc.outs.empty()) return;  // no step: nothing to write
+  summary[0] = n, summary[1] = fc.n_steps, summary[2] = fc.n_instr, summary[3] = fl_min_lanes(fc);
 
-  DBuf<uint32_t> d_code(ctx, fc.code.size()), d_outs(ctx, fc.outs.size());
-  DBuf<u64> d_consts(ctx, std::max<size_t>(fc.consts.size(), 1)), scratch;
-  size_t batch = n;
-  if (!lanes) {
-    batch = (size_t(1) << 30) / (fc.n_slots * 8);  // the scratch stays below ~1 GiB
-    batch = std::min(std::max<size_t>(256, batch & ~size_t(255)), n);
-    scratch = DBuf<u64>(ctx, batch * fc.n_slots);
+  // the passes of all groups in one code, one constant and one output table; where each pass starts, and its row batch
+  struct Run {
+    const FillGroup* g;
+    size_t code0, consts0, outs0, batch;
+    unsigned lanes;
+  };
+  std::vector<Run> runs;
+  std::vector<uint32_t> code, outs;
+  std::vector<u64> consts;
+  size_t scratch_words = 0;
+  bool any_scan = false, all_additive = true;
+  for (const FillGroup& g : fc.groups) {
+    if (g.pass.outs.empty()) continue;  // no step: nothing to write
+    Run r{&g, code.size(), consts.size(), outs.size(), n, fill_lds_lanes(g.pass.n_slots, 8)};
+    if (!r.lanes) {
+      r.batch = (size_t(1) << 30) / (g.pass.n_slots * 8);  // the scratch stays below ~1 GiB
+      r.batch = std::min(std::max<size_t>(256, r.batch & ~size_t(255)), n);
+      scratch_words = std::max(scratch_words, r.batch * g.pass.n_slots);
+    }
+    code.insert(code.end(), g.pass.code.begin(), g.pass.code.end());  // (whole instructions: every pass starts 16-byte aligned)
+    consts.insert(consts.end(), g.pass.consts.begin(), g.pass.consts.end());
+    outs.insert(outs.end(), g.pass.outs.begin(), g.pass.outs.end());
+    any_scan |= g.scan;
+    all_additive &= !g.scan || g.additive;
+    runs.push_back(r);
   }
-  ctx.h2d(d_code.p, fc.code.data(), fc.code.size() * 4);
-  ctx.h2d(d_outs.p, fc.outs.data(), fc.outs.size() * 4);
-  if (!fc.consts.empty()) ctx.h2d(d_consts.p, fc.consts.data(), fc.consts.size() * 8);
+  if (runs.empty()) return;
+  const size_t n_tiles = (n + SC_TILE - 1) / SC_TILE;
+  if (any_scan && n_tiles > (size_t(1) << 31)) fail("the circuit is too high for a scan step");
+
+  DBuf<uint32_t> d_code(ctx, code.size()), d_outs(ctx, outs.size());
+  DBuf<u64> d_consts(ctx, std::max<size_t>(consts.size(), 1)), scratch, tmp, aggs, starts;
+  if (scratch_words) scratch = DBuf<u64>(ctx, scratch_words);
+  if (any_scan) {
+    tmp = DBuf<u64>(ctx, n * (all_additive ? 1 : 2));
+    if (n_tiles > 1) aggs = DBuf<u64>(ctx, 2 * n_tiles), starts = DBuf<u64>(ctx, n_tiles);
+  }
+  ctx.h2d(d_code.p, code.data(), code.size() * 4);
+  ctx.h2d(d_outs.p, outs.data(), outs.size() * 4);
+  if (!consts.empty()) ctx.h2d(d_consts.p, consts.data(), consts.size() * 8);
   ingest_wait_for_producer(ctx, producer_stream);
   try {
     DBuf<u64> inp, bad;
@@ -167,20 +347,35 @@ void witness_fill(HSystem& sys, HWitness& wit, size_t ci, const uint8_t* program
     p.inp = inp.p;
     p.n = n, p.h_in = h_in;
     p.main_w = (uint32_t)c.main_width, p.pre_w = (uint32_t)c.pre_width, p.n_in = (uint32_t)fc.n_inputs;
-    p.code = d_code.p, p.consts = d_consts.p, p.outs = d_outs.p;
-    p.n_instr = (uint32_t)fc.n_instr, p.n_outs = (uint32_t)(fc.outs.size() / 2);
-    p.row0 = 0, p.rows = n, p.scratch = nullptr;
-    if (lanes) {
-      hipLaunchKernelGGL(fill_k<true>, dim3((unsigned)((n + lanes - 1) / lanes)), dim3(lanes), fc.n_slots * lanes * 8, ctx.stream, p);
-    } else {
-      p.scratch = scratch.p;
-      for (size_t r0 = 0; r0 < n; r0 += batch) {
-        p.row0 = r0;
-        p.rows = std::min(batch, n - r0);
-        hipLaunchKernelGGL(fill_k<false>, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, ctx.stream, p);
+    for (const Run& r : runs) {  // the groups in order; a scan group: its coefficient pass into tmp, then the scan
+      const FillPass& pass = r.g->pass;
+      p.out = r.g->scan ? tmp.p : wit.traces[ci].p;
+      p.out_w = r.g->scan ? (r.g->additive ? 1 : 2) : (uint32_t)c.main_width;
+      p.code = d_code.p + r.code0, p.consts = d_consts.p + r.consts0, p.outs = d_outs.p + r.outs0;
+      p.n_instr = (uint32_t)pass.n_instr, p.n_outs = (uint32_t)(pass.outs.size() / 2);
+      p.row0 = 0, p.rows = n, p.scratch = nullptr;
+      if (r.lanes) {
+        hipLaunchKernelGGL(fill_k<true>, dim3((unsigned)((n + r.lanes - 1) / r.lanes)), dim3(r.lanes), pass.n_slots * r.lanes * 8, ctx.stream, p);
+      } else {
+        p.scratch = scratch.p;
+        for (size_t r0 = 0; r0 < n; r0 += r.batch) {
+          p.row0 = r0;
+          p.rows = std::min(r.batch, n - r0);
+          hipLaunchKernelGGL(fill_k<false>, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, ctx.stream, p);
+        }
       }
+      HIP_CHECK(hipGetLastError());
+      if (!r.g->scan) continue;
+      ScParams sp;
+      sp.trace = wit.traces[ci].p, sp.tmp = tmp.p, sp.aggs = aggs.p, sp.starts = n_tiles > 1 ? starts.p : nullptr;
+      sp.n = n, sp.init = r.g->init;
+      sp.main_w = (uint32_t)c.main_width, sp.dst = r.g->dst, sp.n_tiles = (uint32_t)n_tiles;
+      if (r.g->additive)
+        scan_launch<true>(ctx, sp);
+      else
+        scan_launch<false>(ctx, sp);
+      HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(hipGetLastError());
     // SystemWitness::from_stage_1 again for the values the witness holds (checked above: the sweep fits)
     if (held && !lookup_values_device(ctx, c.prefix_prog, wit.traces[ci].p, c.pre_width ? c.d_preprocessed.p : nullptr, n, c.main_width, c.pre_width,
                                       c.args_width, lk.mult.p, lk.args.p))

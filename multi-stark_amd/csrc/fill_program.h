@@ -10,6 +10,12 @@
 // hash-consing unless a column they read was assigned in between). Instances are created operands first, so their order is the
 // instruction order; what no final assignment needs is dropped, and slots are allocated by liveness as build_program does for
 // DProgram. The final instance of every assigned column stays live to the end, where each assigned cell is stored once.
+//
+// A program with SCAN steps (the second format, magic "\0MFILL02") is cut into GROUPS: every scan step is one, every maximal run
+// of ordinary steps between scans is one. The part above (fill_linearise) runs once per ordinary group and, for a scan, once as a
+// COEFFICIENT PASS over its two roots (mul, add), or over the add root alone when the mul root is the constant 1: a pseudo-group
+// whose outputs 0 / 1 go to a temporary instead of the trace and bind no column. A read of a column that an earlier group
+// assigned is an ordinary load of the trace, which that group has finished by then.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -28,95 +34,47 @@ struct FillField {
   uint64_t magic;       // the blob's first word: a program is authored over one field (its constants are folded modulo it)
   uint64_t modulus;     // constants are canonical: below this
   unsigned value_bits;  // bits(x, lo, length) needs lo + length <= value_bits
+  uint64_t scan_magic;  // the first word of a program with scan steps; 0: this configuration has none
 };
-constexpr FillField FILL_GOLDILOCKS{0x31304C4C49464D00ull, 0xFFFFFFFF00000001ull, 64};  // "\0MFILL01"
-constexpr FillField FILL_BABYBEAR{0x3130424C49464D00ull, 0x78000001ull, 32};            // "\0MFILB01"
+constexpr FillField FILL_GOLDILOCKS{0x31304C4C49464D00ull, 0xFFFFFFFF00000001ull, 64, 0x32304C4C49464D00ull};  // "\0MFILL01", "\0MFILL02"
+constexpr FillField FILL_BABYBEAR{0x3130424C49464D00ull, 0x78000001ull, 32, 0};                                // "\0MFILB01"
 
 constexpr uint32_t FL_NONE = ~0u;
 constexpr uint32_t FL_SRC_PRE = 0, FL_SRC_MAIN = 1, FL_SRC_INPUT = 3;
 constexpr size_t FL_MAX_WIDTH = size_t(1) << 20, FL_MAX_NODES = size_t(1) << 24;
 enum : uint32_t { OP_ROW = 16, OP_BITS, OP_INV0, OP_LT, OP_XOR, OP_AND };  // behind the kinds of program.h
 
-struct FillCode {  // a compiled program, on the host
-  size_t main_w = 0, pre_w = 0, n_inputs = 0, n_steps = 0, n_instr = 0, n_slots = 0, n_assigned = 0;
+struct FillPass {  // what one launch of the fill kernel runs
+  size_t n_instr = 0, n_slots = 0;
   std::vector<uint32_t> code;  // [op, dst slot, a, b] per instruction
   std::vector<uint64_t> consts;
-  std::vector<uint32_t> outs;  // (column, slot) per assigned column
+  std::vector<uint32_t> outs;  // (column, slot) per assigned column; a coefficient pass: columns 0 (mul) and 1 (add), or 0 (add) alone
+};
+struct FillGroup {
+  FillPass pass;                        // the ordinary steps of the group / the coefficient pass of the scan
+  bool scan = false, additive = false;  // additive: the mul root is the constant 1, the temporary holds the add root alone
+  uint32_t dst = 0;                     // scan: its column and first value
+  uint64_t init = 0;
+};
+// A compiled program, on the host. n_instr is summed and n_slots the largest over the passes. `groups` holds the passes in the
+// order they run; without scan steps (the first format) there is one group, and code / consts / outs are that group's too.
+struct FillCode : FillPass {
+  size_t main_w = 0, pre_w = 0, n_inputs = 0, n_steps = 0, n_assigned = 0, n_scans = 0, n_additive = 0;
+  std::vector<FillGroup> groups;
 };
 
 inline bool fl_unary(uint32_t k) { return k == OP_NEG || k == OP_INV0 || k == OP_BITS; }
 inline bool fl_binary(uint32_t k) { return k == OP_ADD || k == OP_SUB || k == OP_MUL || k == OP_LT || k == OP_XOR || k == OP_AND; }
 
-inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string& name, const FillField& field) {
+// One group: `steps` (dst, root) in order -> instructions, slots, outputs. `deps`: the node reads, directly or through operands,
+// a main column at offset 0. bind: a read of main column m at offset 0 sees the latest earlier step of the group that assigned
+// m (an ordinary group, out_w = main_width); without it the dsts are output numbers below out_w and no read sees them (a
+// coefficient pass).
+template <class Fail>
+inline FillPass fill_linearise(const std::vector<PNode>& nodes, const std::vector<char>& deps, const std::vector<std::pair<uint32_t, uint32_t>>& steps,
+                               size_t out_w, bool bind, const Fail& fail) {
   typedef uint64_t u64;
-  auto fail = [&](const std::string& what) -> void { throw std::runtime_error(name + ": " + what); };
-  if (!blob) fail("null program");
-  if (len % 8 || len < 48) fail("truncated program blob (" + std::to_string(len) + " bytes)");
-  const size_t nw = len / 8;
-  auto rd = [&](size_t i) {
-    u64 v;
-    memcpy(&v, blob + 8 * i, 8);
-    return v;
-  };
-  if (rd(0) != field.magic) fail("not a fill program (wrong magic)");
-  const u64 main_w = rd(1), pre_w = rd(2), n_in = rd(3), nn = rd(4), ns = rd(5);
-  if (main_w > FL_MAX_WIDTH || pre_w > FL_MAX_WIDTH || n_in > FL_MAX_WIDTH) fail("widths out of range");
-  if (nn > nw / 3 || ns > nw / 2 || 6 + 3 * nn + 2 * ns != nw)
-    fail("truncated program blob: " + std::to_string(nw) + " words for " + std::to_string(nn) + " nodes and " + std::to_string(ns) + " steps");
-  if (nn > FL_MAX_NODES) fail("more than 2^24 nodes");
-  std::vector<PNode> nodes(nn);
-  for (size_t i = 0; i < nn; i++) {
-    const u64 head = rd(6 + 3 * i);
-    if (head >> 24) fail("node " + std::to_string(i) + ": malformed head word");
-    nodes[i].kind = (uint32_t)(head & 0xff), nodes[i].source = (uint32_t)((head >> 8) & 0xff), nodes[i].offset = (uint32_t)(head >> 16);
-    nodes[i].a = rd(7 + 3 * i), nodes[i].b = rd(8 + 3 * i);
-  }
-  std::vector<std::pair<uint32_t, uint32_t>> steps(ns);
-  std::vector<char> assigned(main_w, 0);
-  const size_t s0 = 6 + 3 * nn;
-  for (size_t k = 0; k < ns; k++) {
-    const u64 dst = rd(s0 + 2 * k), root = rd(s0 + 2 * k + 1);
-    if (dst >= main_w) fail("step " + std::to_string(k) + ": dst " + std::to_string(dst) + " is out of range (main_width " + std::to_string(main_w) + ")");
-    if (root >= nn) fail("step " + std::to_string(k) + ": root " + std::to_string(root) + " is out of range");
-    steps[k] = {(uint32_t)dst, (uint32_t)root};
-    assigned[dst] = 1;
-  }
-  std::vector<char> deps(nn, 0);  // reads, directly or through operands, a main column at offset 0
-  for (size_t i = 0; i < nn; i++) {
-    const PNode& n = nodes[i];
-    const std::string at = "node " + std::to_string(i) + ": ";
-    if (n.kind == OP_CONST) {
-      if (n.a >= field.modulus) fail(at + "non-canonical constant");
-    } else if (n.kind == OP_VAR) {
-      if (n.source == 2) fail(at + "stage-2 variables are not allowed in a fill program");
-      if (n.source != FL_SRC_PRE && n.source != FL_SRC_MAIN && n.source != FL_SRC_INPUT) fail(at + "unknown variable source");
-      const u64 width = n.source == FL_SRC_PRE ? pre_w : n.source == FL_SRC_MAIN ? main_w : n_in;
-      if (n.offset > 1) fail(at + "row offset out of range");
-      if (n.a >= width) fail(at + "variable " + std::to_string(n.a) + " of source " + std::to_string(n.source) + " is out of range (width " + std::to_string(width) + ")");
-      if (n.source == FL_SRC_MAIN && n.offset == 1 && assigned[n.a])
-        fail(at + "offset-1 read of main column " + std::to_string(n.a) + ", which the program assigns (the next row may be read only of columns no step assigns)");
-      deps[i] = n.source == FL_SRC_MAIN && n.offset == 0;
-    } else if (n.kind == OP_PUBLIC) {
-      fail(at + "publics are not allowed in a fill program");
-    } else if (n.kind == OP_IS_FIRST || n.kind == OP_IS_LAST || n.kind == OP_IS_TRANS) {
-      fail(at + "selector nodes are not allowed in a fill program (they are polynomials, not flags: use row, lt and inv0)");
-    } else if (n.kind == OP_ROW) {
-    } else if (fl_unary(n.kind)) {
-      if (n.a >= i) fail(at + "forward operand");
-      if (n.kind == OP_BITS) {
-        const u64 lo = n.b & 0xff, length = n.b >> 8;
-        if ((n.b >> 16) || length < 1 || lo + length > field.value_bits)
-          fail(at + "bad bits fields (need 1 <= length and lo + length <= " + std::to_string(field.value_bits) + ")");
-      }
-      deps[i] = deps[n.a];
-    } else if (fl_binary(n.kind)) {
-      if (n.a >= i || n.b >= i) fail(at + "forward operand");
-      deps[i] = deps[n.a] | deps[n.b];
-    } else {
-      fail(at + "unknown node kind " + std::to_string(n.kind));
-    }
-  }
-
+  const size_t nn = nodes.size(), ns = steps.size();
   // ---- linearise: the steps in order, nodes -> hash-consed instances
   struct Inst {
     uint32_t op, a, b;
@@ -134,7 +92,7 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
     known.emplace(key, id);
     return id;
   };
-  std::vector<uint32_t> inst_of(nn, FL_NONE), stamp(nn, FL_NONE), binding(main_w, FL_NONE), stack;
+  std::vector<uint32_t> inst_of(nn, FL_NONE), stamp(nn, FL_NONE), binding(out_w, FL_NONE), stack;
   for (size_t k = 0; k < ns; k++) {
     auto ready = [&](u64 x) { return inst_of[x] != FL_NONE && (!deps[x] || stamp[x] == (uint32_t)k); };
     stack.assign(1, steps[k].second);
@@ -158,7 +116,7 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
       if (n.kind == OP_CONST)
         id = intern(OP_CONST, 0, 0, n.a);
       else if (n.kind == OP_VAR)
-        id = deps[i] && binding[n.a] != FL_NONE ? binding[n.a] : intern(OP_VAR, n.source | (n.offset << 8), (uint32_t)n.a, 0);
+        id = bind && deps[i] && binding[n.a] != FL_NONE ? binding[n.a] : intern(OP_VAR, n.source | (n.offset << 8), (uint32_t)n.a, 0);
       else if (n.kind == OP_ROW)
         id = intern(OP_ROW, 0, 0, 0);
       else if (un)
@@ -177,13 +135,11 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
   const uint32_t INF = 0xFFFFFFFFu;
   std::vector<uint8_t> needed(NI, 0);
   std::vector<uint32_t> last_use(NI, 0), slot_of(NI, INF), free_slots;
-  FillCode out;
-  out.main_w = main_w, out.pre_w = pre_w, out.n_inputs = n_in, out.n_steps = ns;
-  for (size_t m = 0; m < main_w; m++)
+  FillPass out;
+  for (size_t m = 0; m < out_w; m++)
     if (binding[m] != FL_NONE) {
       needed[binding[m]] = 1;
       last_use[binding[m]] = INF;
-      out.n_assigned++;
     }
   auto has_a = [](uint32_t op) { return fl_unary(op) || fl_binary(op); };
   for (size_t i = NI; i-- > 0;) {
@@ -225,10 +181,171 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
     slot_of[i] = dst;
     out.code.insert(out.code.end(), {n.op, dst, a, b});
   }
-  for (size_t m = 0; m < main_w; m++)
+  for (size_t m = 0; m < out_w; m++)
     if (binding[m] != FL_NONE) out.outs.insert(out.outs.end(), {(uint32_t)m, slot_of[binding[m]]});
   out.n_instr = out.code.size() / 4;
   out.n_slots = std::max<uint32_t>(n_slots, 1);
+  return out;
+}
+
+inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string& name, const FillField& field) {
+  typedef uint64_t u64;
+  auto fail = [&](const std::string& what) -> void { throw std::runtime_error(name + ": " + what); };
+  if (!blob) fail("null program");
+  if (len % 8 || len < 48) fail("truncated program blob (" + std::to_string(len) + " bytes)");
+  const size_t nw = len / 8;
+  auto rd = [&](size_t i) {
+    u64 v;
+    memcpy(&v, blob + 8 * i, 8);
+    return v;
+  };
+  const bool v2 = field.scan_magic && rd(0) == field.scan_magic;  // the second format: a seventh header word, scan records at the end
+  if (rd(0) != field.magic && !v2) fail("not a fill program (wrong magic)");
+  const size_t hw = v2 ? 7 : 6;
+  if (nw < hw) fail("truncated program blob (" + std::to_string(len) + " bytes)");
+  const u64 main_w = rd(1), pre_w = rd(2), n_in = rd(3), nn = rd(4), ns = rd(5), nsc = v2 ? rd(6) : 0;
+  if (main_w > FL_MAX_WIDTH || pre_w > FL_MAX_WIDTH || n_in > FL_MAX_WIDTH) fail("widths out of range");
+  if (nn > nw / 3 || ns > nw / 2 || nsc > nw / 3 || hw + 3 * nn + 2 * ns + 3 * nsc != nw)
+    fail("truncated program blob: " + std::to_string(nw) + " words for " + std::to_string(nn) + " nodes and " + std::to_string(ns) + " steps" +
+         (v2 ? " and " + std::to_string(nsc) + " scans" : std::string()));
+  if (nn > FL_MAX_NODES) fail("more than 2^24 nodes");
+  std::vector<PNode> nodes(nn);
+  for (size_t i = 0; i < nn; i++) {
+    const u64 head = rd(hw + 3 * i);
+    if (head >> 24) fail("node " + std::to_string(i) + ": malformed head word");
+    nodes[i].kind = (uint32_t)(head & 0xff), nodes[i].source = (uint32_t)((head >> 8) & 0xff), nodes[i].offset = (uint32_t)(head >> 16);
+    nodes[i].a = rd(hw + 1 + 3 * i), nodes[i].b = rd(hw + 2 + 3 * i);
+  }
+  std::vector<std::pair<uint32_t, uint32_t>> steps(ns);
+  std::vector<char> assigned(main_w, 0);
+  const size_t s0 = hw + 3 * nn;
+  for (size_t k = 0; k < ns; k++) {
+    const u64 dst = rd(s0 + 2 * k), root = rd(s0 + 2 * k + 1);
+    if (dst >= main_w) fail("step " + std::to_string(k) + ": dst " + std::to_string(dst) + " is out of range (main_width " + std::to_string(main_w) + ")");
+    if (root >= nn) fail("step " + std::to_string(k) + ": root " + std::to_string(root) + " is out of range");
+    steps[k] = {(uint32_t)dst, (uint32_t)root};
+    assigned[dst] = 1;
+  }
+  // scan records [step index, mul root, init], step indices strictly ascending
+  struct Scan {
+    size_t step;
+    uint32_t mul;
+    u64 init;
+  };
+  std::vector<Scan> scans(nsc);
+  const size_t c0 = s0 + 2 * ns;
+  for (size_t j = 0; j < nsc; j++) {
+    const u64 step = rd(c0 + 3 * j), mul = rd(c0 + 3 * j + 1), init = rd(c0 + 3 * j + 2);
+    const std::string at = "scan " + std::to_string(j) + ": ";
+    if (step >= ns) fail(at + "step index " + std::to_string(step) + " is out of range (" + std::to_string(ns) + " steps)");
+    if (j && step <= scans[j - 1].step) fail(at + "step index " + std::to_string(step) + " is not above the one before (the records are in ascending order of steps)");
+    if (mul >= nn) fail(at + "mul root " + std::to_string(mul) + " is out of range");
+    if (init >= field.modulus) fail(at + "non-canonical init");
+    scans[j] = Scan{(size_t)step, (uint32_t)mul, init};
+  }
+  std::vector<char> deps(nn, 0);  // reads, directly or through operands, a main column at offset 0
+  for (size_t i = 0; i < nn; i++) {
+    const PNode& n = nodes[i];
+    const std::string at = "node " + std::to_string(i) + ": ";
+    if (n.kind == OP_CONST) {
+      if (n.a >= field.modulus) fail(at + "non-canonical constant");
+    } else if (n.kind == OP_VAR) {
+      if (n.source == 2) fail(at + "stage-2 variables are not allowed in a fill program");
+      if (n.source != FL_SRC_PRE && n.source != FL_SRC_MAIN && n.source != FL_SRC_INPUT) fail(at + "unknown variable source");
+      const u64 width = n.source == FL_SRC_PRE ? pre_w : n.source == FL_SRC_MAIN ? main_w : n_in;
+      if (n.offset > 1) fail(at + "row offset out of range");
+      if (n.a >= width) fail(at + "variable " + std::to_string(n.a) + " of source " + std::to_string(n.source) + " is out of range (width " + std::to_string(width) + ")");
+      if (!v2 && n.source == FL_SRC_MAIN && n.offset == 1 && assigned[n.a])  // (the second format: by groups, below)
+        fail(at + "offset-1 read of main column " + std::to_string(n.a) + ", which the program assigns (the next row may be read only of columns no step assigns)");
+      deps[i] = n.source == FL_SRC_MAIN && n.offset == 0;
+    } else if (n.kind == OP_PUBLIC) {
+      fail(at + "publics are not allowed in a fill program");
+    } else if (n.kind == OP_IS_FIRST || n.kind == OP_IS_LAST || n.kind == OP_IS_TRANS) {
+      fail(at + "selector nodes are not allowed in a fill program (they are polynomials, not flags: use row, lt and inv0)");
+    } else if (n.kind == OP_ROW) {
+    } else if (fl_unary(n.kind)) {
+      if (n.a >= i) fail(at + "forward operand");
+      if (n.kind == OP_BITS) {
+        const u64 lo = n.b & 0xff, length = n.b >> 8;
+        if ((n.b >> 16) || length < 1 || lo + length > field.value_bits)
+          fail(at + "bad bits fields (need 1 <= length and lo + length <= " + std::to_string(field.value_bits) + ")");
+      }
+      deps[i] = deps[n.a];
+    } else if (fl_binary(n.kind)) {
+      if (n.a >= i || n.b >= i) fail(at + "forward operand");
+      deps[i] = deps[n.a] | deps[n.b];
+    } else {
+      fail(at + "unknown node kind " + std::to_string(n.kind));
+    }
+  }
+
+  FillCode out;
+  out.main_w = main_w, out.pre_w = pre_w, out.n_inputs = n_in, out.n_steps = ns, out.n_scans = nsc;
+  for (size_t m = 0; m < main_w; m++) out.n_assigned += assigned[m];
+  typedef std::vector<std::pair<uint32_t, uint32_t>> Steps;
+  if (!v2) {
+    out.groups.resize(1);
+    out.groups[0].pass = fill_linearise(nodes, deps, steps, main_w, true, fail);
+    static_cast<FillPass&>(out) = out.groups[0].pass;
+    return out;
+  }
+
+  // ---- the second format: groups in order, [first step, last step) with the scan record of a scan group
+  struct Range {
+    size_t lo, hi;
+    const Scan* scan;
+  };
+  std::vector<Range> ranges;
+  size_t at_step = 0;
+  for (const Scan& sc : scans) {
+    if (sc.step > at_step) ranges.push_back(Range{at_step, sc.step, nullptr});
+    ranges.push_back(Range{sc.step, sc.step + 1, &sc});
+    at_step = sc.step + 1;
+  }
+  if (ns > at_step) ranges.push_back(Range{at_step, (size_t)ns, nullptr});
+  // the offset-1 rule: group g may read the next row of main column m only if no step of group g or of a later group assigns m
+  const uint32_t NG = (uint32_t)ranges.size();
+  std::vector<uint32_t> last_group(main_w, FL_NONE);  // the last group that assigns the column
+  for (uint32_t g = 0; g < NG; g++)
+    for (size_t k = ranges[g].lo; k < ranges[g].hi; k++) last_group[steps[k].first] = g;
+  std::vector<uint32_t> seen(nn, FL_NONE), stack;
+  for (uint32_t g = 0; g < NG; g++) {
+    const Range& rg = ranges[g];
+    for (size_t k = rg.lo; k < rg.hi; k++) stack.push_back(steps[k].second);
+    if (rg.scan) stack.push_back(rg.scan->mul);
+    while (!stack.empty()) {
+      const uint32_t i = stack.back();
+      stack.pop_back();
+      if (seen[i] == g) continue;
+      seen[i] = g;
+      const PNode& n = nodes[i];
+      if (fl_unary(n.kind) || fl_binary(n.kind)) stack.push_back((uint32_t)n.a);
+      if (fl_binary(n.kind)) stack.push_back((uint32_t)n.b);
+      if (n.kind != OP_VAR || n.source != FL_SRC_MAIN) continue;
+      if (rg.scan && n.a == steps[rg.lo].first)
+        fail("step " + std::to_string(rg.lo) + ": the coefficients of a scan step read its own dst, main column " + std::to_string(n.a) + " at offset " +
+             std::to_string(n.offset) + " (node " + std::to_string(i) + "; the previous row's value enters through the recurrence alone)");
+      if (n.offset == 1 && last_group[n.a] != FL_NONE && last_group[n.a] >= g)
+        fail("node " + std::to_string(i) + ": offset-1 read of main column " + std::to_string(n.a) + " by step group " + std::to_string(g) +
+             ", which step group " + std::to_string(last_group[n.a]) + " assigns (the next row may be read only of columns that no step of the same or a later group assigns)");
+    }
+  }
+  for (const Range& rg : ranges) {
+    FillGroup gr;
+    if (!rg.scan) {
+      gr.pass = fill_linearise(nodes, deps, Steps(steps.begin() + rg.lo, steps.begin() + rg.hi), main_w, true, fail);
+    } else {
+      const uint32_t mul = rg.scan->mul, add = steps[rg.lo].second;
+      gr.scan = true, gr.dst = steps[rg.lo].first, gr.init = rg.scan->init;
+      gr.additive = nodes[mul].kind == OP_CONST && nodes[mul].a == 1;
+      gr.pass = gr.additive ? fill_linearise(nodes, deps, Steps{{0, add}}, 1, false, fail) : fill_linearise(nodes, deps, Steps{{0, mul}, {1, add}}, 2, false, fail);
+      out.n_additive += gr.additive;
+    }
+    out.n_instr += gr.pass.n_instr;
+    out.n_slots = std::max(out.n_slots, gr.pass.n_slots);
+    out.groups.push_back(std::move(gr));
+  }
+  out.n_slots = std::max<size_t>(out.n_slots, 1);
   return out;
 }
 

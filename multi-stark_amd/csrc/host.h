@@ -238,6 +238,8 @@ void witness_fill(HSystem& sys, HWitness& wit, size_t ci, const uint8_t* program
                   void* producer_stream, u64 summary[4]);
 // ms_fill_program_info: host only - [instructions, live slots, lanes of the LDS form (0: global scratch), assigned columns]
 void fill_program_info(const uint8_t* program, size_t program_len, u64 out4[4]);
+// ms_fill_scan_info: host only - [scan steps, launches of the fill kernel, scans in the additive form, rows per scan tile]
+void fill_scan_info(const uint8_t* program, size_t program_len, u64 out4[4]);
 void field_op(Ctx& ctx, int op, const u64* a, const u64* b, size_t n, u64* out);
 
 }  // namespace msamd

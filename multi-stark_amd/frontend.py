@@ -657,41 +657,126 @@ class _FillInterner(_Interner):
         return {N_ADD: self.add, N_SUB: self.sub, N_MUL: self.mul, N_LT: self.lt, N_XOR: self.xor, N_AND: self.and_}[k](a, b)
 
 
-def fill_blob(main_width, preprocessed_width, n_inputs, nodes, steps):
+FILL_SCAN_MAGIC = 0x32304C4C49464D00  # "\0MFILL02": a program with scan steps (Goldilocks configuration only)
+
+
+class Scan:
+    """The right-hand side of a scan step (scan, running_sum, running_product): dst[0] = init, dst[r + 1] = mul(r) * dst[r] + add(r)"""
+
+    __slots__ = ("mul", "add", "init")
+
+    def __init__(self, mul, add, init):
+        self.mul, self.add, self.init = Expr.lift(mul), Expr.lift(add), int(init)
+
+
+def scan(mul, add, init=0):
+    """A column that follows its previous row, usable only as the right-hand side of a step of compile_fill: the column starts
+    at init (an integer in [0, P)) and row r + 1 is mul * previous + add with both expressions taken at row r (no wrap-around:
+    their values at the last row are not used). The expressions may not read the column itself."""
+    return Scan(mul, add, init)
+
+
+def running_sum(add, init=0):
+    """scan(1, add, init): the additive form on the device, no multiplications"""
+    return Scan(1, add, init)
+
+
+def running_product(mul, init=1):
+    return Scan(mul, 0, init)
+
+
+def fill_blob(main_width, preprocessed_width, n_inputs, nodes, steps, scans=None):
     """The little-endian u64-word blob of a fill program, unchecked: magic, main_width, pre_width, n_inputs, n_nodes, n_steps,
-    the nodes as [kind | source << 8 | offset << 16, a, b], the steps as [dst, root]."""
+    the nodes as [kind | source << 8 | offset << 16, a, b], the steps as [dst, root]. With scans (a non-empty list of
+    (step index, mul root, init)): the magic of the second format, n_scans as a seventh header word, and the scan records
+    behind the steps; the root of a scan step is its add root."""
     words = [FILL_MAGIC, main_width, preprocessed_width, n_inputs, len(nodes), len(steps)]
+    if scans:
+        words[0] = FILL_SCAN_MAGIC
+        words.append(len(scans))
     for (kind, source, offset, a, b) in nodes:
         words += [kind | (source << 8) | (offset << 16), a, b]
     for (dst, root) in steps:
         words += [dst, root]
+    for (step, mul, init) in scans or []:
+        words += [step, mul, init]
     return np.asarray(words, dtype=np.uint64).tobytes()
 
 
 class FillProgram:
-    """What compile_fill returns: .nodes (kind, source, offset, a, b), .steps (dst, root), the widths and .blob"""
+    """What compile_fill returns: .nodes (kind, source, offset, a, b), .steps (dst, root; a scan step's root is its add root),
+    .scans (step index, mul root, init), the widths and .blob"""
 
-    def __init__(self, main_width, preprocessed_width, n_inputs, nodes, steps):
+    def __init__(self, main_width, preprocessed_width, n_inputs, nodes, steps, scans=()):
         self.main_width, self.preprocessed_width, self.n_inputs = main_width, preprocessed_width, n_inputs
-        self.nodes, self.steps = nodes, steps
-        self.blob = fill_blob(main_width, preprocessed_width, n_inputs, nodes, steps)
+        self.nodes, self.steps, self.scans = nodes, steps, list(scans)
+        self.blob = fill_blob(main_width, preprocessed_width, n_inputs, nodes, steps, self.scans)
+
+
+def _main_reads(nodes):
+    """per node: the main columns it reads, directly or through operands, as (at offset 0, at offset 1)"""
+    reads = []
+    for (kind, source, offset, a, b) in nodes:
+        if kind == N_VAR:
+            cols = frozenset([a]) if source == SRC_MAIN else frozenset()
+            reads.append((frozenset(), cols) if offset else (cols, frozenset()))
+        elif kind in (N_NEG, N_INV0, N_BITS):
+            reads.append(reads[a])
+        elif kind in (N_ADD, N_SUB, N_MUL, N_LT, N_XOR, N_AND):
+            reads.append((reads[a][0] | reads[b][0], reads[a][1] | reads[b][1]))
+        else:
+            reads.append((frozenset(), frozenset()))
+    return reads
 
 
 def compile_fill(main_width, preprocessed_width, n_inputs, steps):
-    """steps: [(dst_column, Expr)], run in order for every row (include/mstark.h, ms_witness_fill). -> FillProgram"""
+    """steps: [(dst_column, Expr or scan(...))], run in order, each for every row (include/mstark.h, ms_witness_fill).
+    Every scan step is a group of its own and every run of ordinary steps between scans is one; the next row of a main column
+    may be read only where no step of the same or a later group assigns it. -> FillProgram"""
     spec = {"main_width": int(main_width), "preprocessed_width": int(preprocessed_width), "n_inputs": int(n_inputs)}
     it = _FillInterner()
-    out = []
+    out, scans = [], []
     for k, (dst, e) in enumerate(steps):
         dst = int(dst)
         if not 0 <= dst < spec["main_width"]:
             raise CompileError("DstOutOfRange step=%d dst=%d main_width=%d" % (k, dst, spec["main_width"]))
+        if isinstance(e, Scan):
+            if FILL_MAGIC != GOLDILOCKS["FILL_MAGIC"]:
+                raise CompileError("ScanStepInThisField step=%d: scan steps: Goldilocks configuration only" % k)
+            if not 0 <= e.init < P:
+                raise CompileError("ScanInitOutOfRange step=%d init=%d: the first value of a scan column is an integer in [0, P)" % (k, e.init))
+            scans.append((k, it.compile_fill_expr(e.mul, spec), e.init))
+            e = e.add
         out.append((dst, it.compile_fill_expr(Expr.lift(e), spec)))
-    assigned = {dst for dst, _ in out}
-    for (kind, source, offset, a, _) in it.nodes:
-        if kind == N_VAR and source == SRC_MAIN and offset == 1 and a in assigned:
-            raise CompileError("NextRowOfAssignedColumn column=%d: a fill program may read the next row only of columns it does not assign" % a)
-    return FillProgram(spec["main_width"], spec["preprocessed_width"], spec["n_inputs"], it.nodes, out)
+    if not scans:
+        assigned = {dst for dst, _ in out}
+        for (kind, source, offset, a, _) in it.nodes:
+            if kind == N_VAR and source == SRC_MAIN and offset == 1 and a in assigned:
+                raise CompileError("NextRowOfAssignedColumn column=%d: a fill program may read the next row only of columns it does not assign" % a)
+        return FillProgram(spec["main_width"], spec["preprocessed_width"], spec["n_inputs"], it.nodes, out)
+    # groups: a scan step is one, a run of ordinary steps between scans is one
+    mul_of = {k: mul for k, mul, _ in scans}
+    group, g = [], -1
+    for k in range(len(out)):
+        if k in mul_of or k == 0 or (k - 1) in mul_of:
+            g += 1
+        group.append(g)
+    last_group = {}
+    for k, (dst, _) in enumerate(out):
+        last_group[dst] = group[k]
+    reads = _main_reads(it.nodes)
+    for k, (dst, root) in enumerate(out):
+        roots = [root] + ([mul_of[k]] if k in mul_of else [])
+        at0 = frozenset().union(*(reads[r][0] for r in roots))
+        at1 = frozenset().union(*(reads[r][1] for r in roots))
+        if k in mul_of and dst in at0 | at1:
+            raise CompileError("ScanReadsOwnColumn step=%d column=%d: the coefficients of a scan step may not read its own column "
+                               "(the previous row's value enters through the recurrence alone)" % (k, dst))
+        for m in sorted(at1):
+            if last_group.get(m, -1) >= group[k]:
+                raise CompileError("NextRowOfAssignedColumn column=%d step=%d: the next row may be read only of columns that no step of "
+                                   "the same or a later group assigns (group %d reads, group %d assigns)" % (m, k, group[k], last_group[m]))
+    return FillProgram(spec["main_width"], spec["preprocessed_width"], spec["n_inputs"], it.nodes, out, scans)
 
 
 def u32_add_fill_program(num_adds):

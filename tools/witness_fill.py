@@ -17,6 +17,12 @@ frontend.u32_add_halves_fill_program (a field below 2^31 cannot hold x + y), Byt
 (msbb_witness_derive_multiplicities), and the result is compared with the host builder's traces and, proof bytes against proof
 bytes, with the host-built witness. There is no BabyBear generator in HBM, so two routes alternate: fill + derive (and
 msbb_witness_fill alone) against the host route, frontend._u32_add_traces (numpy) and msbb_witness_create.
+  python tools/witness_fill.py --scan [--log-size 20] [--reps 9]
+--scan: the price of scan steps. A test circuit of 16 columns is filled by the U32Add program plus a Horner accumulator
+(acc' = acc * alpha + the sum word) and a running sum of the carries; the routes alternate: ms_witness_fill with the two scans,
+the same program without them (the difference is what the scans cost), the running sum alone in the additive form (multiplier
+the constant 1) and in the affine form (multiplier an input column of ones), and the host route the scans replace -
+ms_witness_trace, one sequential loop over the rows, ms_witness_create.
 Timing: wall time of each route (all return synchronised), alternating after two warm-up rounds; median, minimum and maximum are
 printed. No figure here is a share of peak."""
 import argparse
@@ -36,6 +42,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="goldilocks", choices=["goldilocks", "babybear"])
 ap.add_argument("--log-size", type=int, default=20)
 ap.add_argument("--reps", type=int, default=9)
+ap.add_argument("--scan", action="store_true", help="the scan-step leg (Goldilocks)")
 args = ap.parse_args()
 
 pkg = load_package()
@@ -121,8 +128,96 @@ def babybear():
     state.clear()  # witnesses go before their system
 
 
+def scan_leg():
+    """--scan: what scan steps cost. One circuit of 16 columns: the 14 of U32Add, a Horner accumulator over the sum words
+    (column 14) and a running sum of the carries (column 15)."""
+    E = fe.Expr
+    alpha = (1 << 32) + 3
+    x, y, one = E.input(0), E.input(1), E.input(2)
+    s = x + y
+    plain = [(k, fe.bits(x, 8 * k, 8)) for k in range(4)] + [(4 + k, fe.bits(y, 8 * k, 8)) for k in range(4)]
+    plain += [(8 + k, fe.bits(s, 8 * k, 8)) for k in range(4)] + [(12, fe.bits(s, 32, 1)), (13, fe.lt(E.row(), n))]
+    z = E.main(8) + E.main(9) * 256 + E.main(10) * 65536 + E.main(11) * (1 << 24)
+    scans = [(14, fe.scan(alpha, z)), (15, fe.running_sum(E.main(12)))]
+    prog_scans, prog_plain = fe.compile_fill(16, 0, 3, plain + scans), fe.compile_fill(16, 0, 3, plain)
+    sum_additive = fe.compile_fill(16, 0, 3, [(15, fe.running_sum(E.main(12)))])
+    sum_affine = fe.compile_fill(16, 0, 3, [(15, fe.scan(one, E.main(12)))])  # the multiplier as a column of ones: the affine form
+    for name, p in (("with the two scans", prog_scans), ("without them", prog_plain), ("running sum, additive", sum_additive),
+                    ("running sum, affine", sum_affine)):
+        print("program %-24s %d steps; %s; scan info %s" % (name + ":", len(p.steps), pkg.fill_program_info(p), pkg.fill_scan_info(p)))
+    system = pkg.System.new(ctx, fe.bench_params(), [fe.CircuitInputs(16, None, [E.main(12) * E.main(12) - E.main(12)], [], [])])
+    xs, ys = fe.xorshift_pairs(n)
+    packed = fe.pack_claims([])
+    inputs = torch.from_numpy(np.stack([xs, ys, np.ones_like(xs)], axis=1).astype(np.uint32).view(np.int32)).cuda()
+    w = system.witness_from_device([torch.zeros((n, 16), dtype=torch.int64, device="cuda")], packed)
+
+    def host_loop(t):
+        """the two columns as the host makes them: one sequential loop over the rows"""
+        zs = (t[:, 8] + t[:, 9] * 256 + t[:, 10] * 65536 + t[:, 11] * (1 << 24)).tolist()
+        cs = t[:, 12].tolist()
+        acc, run, p = 0, 0, fe.P
+        h, r = [0] * n, [0] * n
+        for i in range(n):
+            h[i], r[i] = acc, run
+            acc, run = (alpha * acc + zs[i]) % p, run + cs[i]
+        t[:, 14], t[:, 15] = np.array(h, dtype=np.uint64), np.array(r, dtype=np.uint64)
+        return t
+
+    rep = w.fill(0, prog_scans, inputs)
+    print("2^%d rows, filled with the scans: %s" % (args.log_size, rep))
+    want = np.zeros((n, 16), dtype=np.uint64)
+    want[:, :14] = fe._u32_add_traces(xs, ys, n)[0][1]
+    want = host_loop(want)
+    same = bool(np.array_equal(w.trace(0), want))
+    w.fill(0, sum_affine, inputs)
+    same_affine = bool(np.array_equal(w.trace(0), want))
+    print("trace equals the host's: %s; the running sum again in the affine form: %s" % (same, same_affine), flush=True)
+    assert same and same_affine
+
+    print("\n# the routes, alternating")
+    state = {}
+
+    def fill(prog):
+        def run():
+            w.fill(0, prog, inputs)
+            ctx.sync()
+        return run
+
+    def host_read():
+        state["t"] = w.trace(0)
+
+    def host_scan():
+        state["t"] = host_loop(state["t"])
+
+    def host_create():
+        state["host"] = None  # (the previous upload's memory goes back first)
+        state["host"] = system.witness([state["t"]], packed)
+
+    t_sc, t_pl, t_add, t_aff, t_rd, t_lp, t_cr = timed([fill(prog_scans), fill(prog_plain), fill(sum_additive), fill(sum_affine), host_read, host_scan,
+                                                        host_create], args.reps)
+    line("ms_witness_fill with the two scans", t_sc)
+    line("ms_witness_fill without them", t_pl)
+    line("running sum alone, additive form", t_add)
+    line("running sum alone, affine form (multiplier column)", t_aff)
+    line("host: ms_witness_trace", t_rd)
+    line("host: the sequential loop (Python integers)", t_lp)
+    line("host: ms_witness_create", t_cr)
+    total = [a + b + c for a, b, c in zip(t_rd, t_lp, t_cr)]
+    moved = [a + c for a, c in zip(t_rd, t_cr)]
+    line("host route, the three steps together", total)
+    line("host route without its loop (read back + create)", moved)
+    m = statistics.median
+    print("the two scans cost %.3f ms; host route / fill = %.0f, without the loop %.1f; affine / additive = %.2f" % (
+        m(t_sc) - m(t_pl), m(total) / m(t_sc), m(moved) / m(t_sc), m(t_aff) / m(t_add)))
+    assert np.array_equal(w.trace(0), want)
+    state.clear()  # witnesses go before their system
+
+
 if args.config == "babybear":
     babybear()
+    sys.exit(0)
+if args.scan:
+    scan_leg()
     sys.exit(0)
 
 system = pkg.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs())
