@@ -622,7 +622,12 @@ int32_t ms_blake3(ms_ctx* ctx, const uint8_t* bytes, size_t len, uint8_t out32[3
  * log_final_poly_len, max_log_arity, num_queries, commit_proof_of_work_bits, query_proof_of_work_bits].
  * ms_pcs_commit: evaluations over the natural domains (row-major, heights[i] x widths[i]) -> coset LDE + Merkle tree, all
  * kept on the device behind ms_mmcs. ms_pcs_open: one ms_mmcs per round; n_points has one entry per matrix (rounds
- * flattened, at most two points per matrix), points holds (c0, c1) per point; opened values are written in
+ * flattened, at most two points per matrix), points holds (c0, c1) per point. Over ALL rounds the matrices of one LDE
+ * height may be opened at no more than two distinct points; a pair (z, z g), g the generator of the matrix's trace domain,
+ * counts as two. A third point at a height fails with MS_ERR ("more than two opening points at one LDE height") after
+ * the opened values have been absorbed: the context stays usable, the challenger has been advanced and must be restarted
+ * from a fresh one. (Plonky3 has no such limit, and neither has msbb_pcs_open, which keeps the limit of two points per
+ * matrix only.) A matrix may have no point; so may every matrix of a height or of a round. Opened values are written in
  * round -> matrix -> point -> column order (2 words each); fri_out receives the FriProof (the opening_proof field of
  * Proof::to_bytes); MS_ERR_BUFFER with *fri_len = needed size if a capacity is too small (the challenger has then been
  * advanced: restart from a fresh one). ms_pcs_verify: the same rounds described by their caps (32-byte digests), log2 domain
