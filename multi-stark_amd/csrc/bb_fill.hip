@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void bb_fill_k(BflParams p) {
 
 void fill_program_info(const uint8_t* program, size_t program_len, u64 out4[4]) {
   const FillCode fc = fill_compile(program, program_len, "msbb_fill_program_info", FILL_BABYBEAR);
-  out4[0] = fc.n_instr, out4[1] = fc.n_slots, out4[2] = fill_lds_lanes(fc.n_slots, 4), out4[3] = fc.n_assigned;
+  out4[0] = fc.n_instr, out4[1] = fc.n_slots, out4[2] = slot_lds_lanes(fc.n_slots, 4, 0), out4[3] = fc.n_assigned;
 }
 
 void witness_fill(BSystem& sys, BWitness& wit, size_t ci, const uint8_t* program, size_t program_len, const ms_dev_matrix* inputs,
@@ -131,7 +131,7 @@ void witness_fill(BSystem& sys, BWitness& wit, size_t ci, const uint8_t* program
       }
     }
   }
-  const unsigned lanes = fill_lds_lanes(fc.n_slots, 4);
+  const unsigned lanes = slot_lds_lanes(fc.n_slots, 4, 0);
   summary[0] = n, summary[1] = fc.n_steps, summary[2] = fc.n_instr, summary[3] = lanes;
   if (fc.outs.empty()) return;  // no step: nothing to write
 
@@ -140,8 +140,7 @@ void witness_fill(BSystem& sys, BWitness& wit, size_t ci, const uint8_t* program
   DBuf<u32> d_consts(ctx, std::max<size_t>(consts.size(), 1)), scratch;
   size_t batch = n;
   if (!lanes) {
-    batch = (size_t(1) << 30) / (fc.n_slots * 4);  // the scratch stays below ~1 GiB
-    batch = std::min(std::max<size_t>(256, batch & ~size_t(255)), n);
+    batch = slot_scratch_rows(fc.n_slots, 4, n);
     scratch = DBuf<u32>(ctx, batch * fc.n_slots);
   }
   ctx.h2d(d_code.p, fc.code.data(), fc.code.size() * 4);

@@ -9,8 +9,9 @@
 //
 // Device side: fill_k, one thread per row. The slot file is [slot][lane] - in LDS at 256 / 128 / 64 lanes per workgroup (lane l
 // touches the 8-byte words slot * lanes + l: consecutive lanes, consecutive words, no bank conflict), or, when it does not fit
-// 64 KB at 64 lanes, in a global scratch walked in row batches (tiers 1 and 4 of check.hip). Rows are independent: offset-1
-// reads of the main trace are refused for every column the program assigns, so no thread reads what another one writes.
+// 64 KB at 64 lanes, in a global scratch walked in row batches (tiers 1 and 4 of check_dev.h, by the placement rules of
+// msamd.h). Rows are independent: offset-1 reads of the main trace are refused for every column the program assigns, so no
+// thread reads what another one writes.
 //
 // Order on the context's stream: program upload, [wait for the producer's stream, ingest of the inputs into a row-major
 // temporary with the offender word, ONE host wait for that word], fill_k, lookup_values_k when the witness holds lookup values
@@ -231,7 +232,7 @@ void scan_launch(Ctx& ctx, const ScParams& p) {
 
 unsigned fl_min_lanes(const FillCode& fc) {
   unsigned lanes = 256;
-  for (const FillGroup& g : fc.groups) lanes = std::min(lanes, fill_lds_lanes(g.pass.n_slots, 8));
+  for (const FillGroup& g : fc.groups) lanes = std::min(lanes, slot_lds_lanes(g.pass.n_slots, 8, 0));
   return lanes;
 }
 
@@ -301,10 +302,9 @@ void witness_fill(HSystem& sys, HWitness& wit, size_t ci, const uint8_t* program
   bool any_scan = false, all_additive = true;
   for (const FillGroup& g : fc.groups) {
     if (g.pass.outs.empty()) continue;  // no step: nothing to write
-    Run r{&g, code.size(), consts.size(), outs.size(), n, fill_lds_lanes(g.pass.n_slots, 8)};
+    Run r{&g, code.size(), consts.size(), outs.size(), n, slot_lds_lanes(g.pass.n_slots, 8, 0)};
     if (!r.lanes) {
-      r.batch = (size_t(1) << 30) / (g.pass.n_slots * 8);  // the scratch stays below ~1 GiB
-      r.batch = std::min(std::max<size_t>(256, r.batch & ~size_t(255)), n);
+      r.batch = slot_scratch_rows(g.pass.n_slots, 8, n);
       scratch_words = std::max(scratch_words, r.batch * g.pass.n_slots);
     }
     code.insert(code.end(), g.pass.code.begin(), g.pass.code.end());  // (whole instructions: every pass starts 16-byte aligned)

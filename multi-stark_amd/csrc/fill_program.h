@@ -349,11 +349,4 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
   return out;
 }
 
-// lanes per workgroup with the slot file in LDS (0: it does not fit 64 KB at 64 lanes); slot_bytes 8 / 4
-inline unsigned fill_lds_lanes(size_t n_slots, size_t slot_bytes) {
-  for (unsigned th = 256; th >= 64; th >>= 1)
-    if (n_slots * th * slot_bytes <= 64 * 1024) return th;
-  return 0;
-}
-
 }  // namespace msamd

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <map>
@@ -48,7 +49,7 @@ enum KernelId : int {
   K_FRI_FOLD,
   K_TRANSPOSE,
   K_OTHER,
-  K_WITNESS_CHECK,    // constraint roots on the trace domain (check.hip, ms_witness_check)
+  K_WITNESS_CHECK,    // constraint roots on the trace domain (check_dev.h, ms_witness_check / msbb_witness_check)
   K_COUNT
 };
 const char* kernel_name(int id);
@@ -415,6 +416,19 @@ struct DProgram {
   DBuf<uint32_t> wave_lookup_off;  // where each lookup starts in wave_lookups
   size_t wave_steps = 0, wave_leaf_steps = 0;
 };
+// where the slot file of a thread-per-row sweep lives (witness check, witness fill; slot_bytes 8 / 4): in LDS as [slot][lane]
+// behind `header_bytes`, at the largest of 256 / 128 / 64 lanes per workgroup that fits 64 KB (0: none does) ...
+inline unsigned slot_lds_lanes(size_t n_slots, size_t slot_bytes, size_t header_bytes) {
+  for (unsigned th = 256; th >= 64; th >>= 1)
+    if (n_slots * th * slot_bytes + header_bytes <= 64 * 1024) return th;
+  return 0;
+}
+// ... or in a global scratch walked in batches of this many rows: a multiple of 256 (at least 256, at most n) that keeps the
+// scratch below ~1 GiB
+inline size_t slot_scratch_rows(size_t n_slots, size_t slot_bytes, size_t n) {
+  const size_t batch = (size_t(1) << 30) / (n_slots * slot_bytes);
+  return std::min(std::max<size_t>(256, batch & ~size_t(255)), n);
+}
 struct QDyn;  // quotient_params.h: the challenge-dependent part of a quotient launch, in device memory
 struct QuotientArgs {
   const u64 *pre = nullptr, *s1 = nullptr, *s2 = nullptr;  // column-major LDEs (bit-reversed rows)

@@ -1,4 +1,4 @@
-"""`-m gpu`: msbb_witness_check (csrc/bb_check.hip) against the model of tests/witness_check_model_bb.py, which
+"""`-m gpu`: msbb_witness_check (csrc/bb_check.hip over csrc/check_dev.h) against the model of tests/witness_check_model_bb.py, which
 tests/test_bb_witness_check_model.py anchors to the BabyBear oracle. Every figure of the report is deterministic and compared
 exactly. References (model reports, traces) are computed once per case and left unchanged. The counterpart of
 test_gpu_witness_check.py; shapes are the smallest that still reach the code named."""
@@ -236,7 +236,7 @@ def chain_trace(pairs, n, width):
     return _CHAIN[key].copy()
 
 
-# bb_check.hip: a slot file of s 4-byte slots runs with slots in LDS at the largest of 256 / 128 / 64 lanes with
+# check_dev.h over bb_check.hip's 4-byte words: a slot file of s 4-byte slots runs with slots in LDS at the largest of 256 / 128 / 64 lanes with
 # s * lanes * 4 + 192 <= 64 KB: 256 lanes up to s = 63, 128 up to 127, 64 up to 255. Above that: a program with a wave schedule
 # (>= 1024 needed nodes, at most 160 KB of 8-byte positions - a sum chain of depth 1278 has none) and <= 16384 rows takes the
 # wave-per-row form; else <= 8192 rows (256 workgroups of 32 lanes) with s * 128 + 192 <= 160 KB, s <= 1278, take the few-lanes

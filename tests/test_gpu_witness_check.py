@@ -1,4 +1,4 @@
-"""`-m gpu`: ms_witness_check (csrc/check.hip) against the model of tests/witness_check_model.py, which
+"""`-m gpu`: ms_witness_check (csrc/check.hip over csrc/check_dev.h) against the model of tests/witness_check_model.py, which
 tests/test_witness_check_model.py anchors to the oracle. Every figure of the report is deterministic and compared exactly.
 References (model reports, traces) are computed once per case and left unchanged."""
 import importlib
@@ -241,7 +241,7 @@ def chain_trace(pairs, n, width=40):
     return _CHAIN[key].copy()
 
 
-# check.hip: a slot file of s slots runs with slots in LDS at the largest of 256 / 128 / 64 lanes with (s * lanes + 24) * 8 <= 64 KB:
+# check_dev.h over check.hip's 8-byte words: a slot file of s slots runs with slots in LDS at the largest of 256 / 128 / 64 lanes with (s * lanes + 24) * 8 <= 64 KB:
 # 256 lanes up to s = 31, 128 up to 63, 64 up to 127. Above that: a program with a wave schedule (>= 1024 needed nodes, at most
 # 160 KB of positions - a sum chain of depth 600 has none) and <= 16384 rows takes the wave-per-row form; else <= 8192 rows
 # (256 workgroups of 32 lanes) with (s * 32 + 24) * 8 <= 160 KB, s <= 639, take the few-lanes form; the rest the global scratch.

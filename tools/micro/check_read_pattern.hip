@@ -1,4 +1,4 @@
-// Does staging a tile of rows through LDS pay for a thread-per-row sweep over a ROW-MAJOR trace (csrc/check.hip)?
+// Does staging a tile of rows through LDS pay for a thread-per-row sweep over a ROW-MAJOR trace (csrc/check_dev.h with check.hip's view)?
 //   hipcc -O3 --offload-arch=gfx950 -o check_read_pattern tools/micro/check_read_pattern.hip && ./check_read_pattern [log2 rows = 20]
 // Both kernels read every word of row r and row (r + 1) mod n once per thread, as the check's leaf loads do, fold them into one
 // word per row and write it: `direct` loads straight from global memory (lane k reads address base + k * width: strided),
