@@ -419,7 +419,30 @@ int32_t ms_witness_derive_multiplicities(ms_witness* w, const ms_mult_target* ta
  * them uses the global scratch).
  *   MS_ERR in addition, before anything is written: a length that does not match the three counts; a scan record whose step
  * index is out of range or not above the one before, whose mul root is out of range or whose init is >= p; a scan step whose
- * coefficients read its own dst; an offset-1 read that the group rule refuses. msbb_witness_fill refuses the blob by its magic. */
+ * coefficients read its own dst; an offset-1 read that the group rule refuses. msbb_witness_fill refuses the blob by its magic.
+ *
+ *   INDEXED READS: a column of a source at a COMPUTED row - the input row of the item a row belongs to (several rows per item),
+ * a sorted or permuted copy of a column (sorted[r] = log[perm[r]]), the table row a lookup points at, a finished running sum at
+ * a segment boundary. Node kind 22, `at`: the head word is 22 | source << 8 and its offset field must be 0; a is the column; b
+ * is the index of an EARLIER node, the row operand. Sources: 0 preprocessed, 1 main, 3 input; stage 2 (source 2) is refused as
+ * for variables.
+ *   Value at row r. Let i be the value of node b at row r, taken as the canonical integer in [0, p), and h the height of the
+ * source: n for the main and the preprocessed trace, the input matrix's own height for inputs. If i < h the node is the
+ * source's column a at row i; if i >= h it is 0. There is no reduction modulo n and no truncation of the index: an index of
+ * 2^32 + 1 reads 0, not row 1. The bound check is the definition: no index a program can compute addresses memory outside the
+ * three matrices, and a row >= h performs no load.
+ *   Main column m. If an earlier group assigned m, `at` sees that group's values, from the trace; if no step assigns m it sees
+ * what the trace held before the call; if a step of the same group or of a later group assigns m the program is refused. This
+ * is the offset-1 rule applied to `at`, in the first format (one group) and in the second, and as there it is what makes the
+ * row-parallel execution equal to the column-at-a-time definition. It follows that the coefficients of a scan step cannot
+ * index their own dst, while a later group may index a finished scan column. In the first format the rule holds for every
+ * node, in the second for the nodes a group reaches, like the offset-1 rule.
+ *   Unchanged: the magic words - a program without an `at` node keeps its blob byte for byte, and a library that predates the
+ * node refuses a program with one as "unknown node kind 22" - the host waits, the summary words (an `at` is one instruction,
+ * equal reads are issued once per launch), the held-lookup recomputation and every refusal above.
+ *   MS_ERR in addition, before anything is written: an `at` node with a forward row operand, a column out of range for its
+ * source's width, a non-zero offset field, a stage-2 or unknown source; an `at` of a main column that the group rule refuses,
+ * naming node, column, reading group and assigning group. */
 int32_t ms_witness_fill(ms_witness* w, size_t circuit, const uint8_t* program, size_t program_len,
                         const ms_dev_matrix* inputs /* nullable with n_inputs 0 */, void* producer_stream /* hipStream_t, nullable */,
                         uint64_t summary[4]);

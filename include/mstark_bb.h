@@ -167,6 +167,10 @@ int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target
  *   Values: operands are the canonical integers in [0, p). bits(x, lo, length) needs 1 <= length and lo + length <= 32;
  * xor(x, y) = (x ^ y) mod p, one conditional subtraction as x ^ y < 2^31 < 2 p; and, lt, inv0 (0 -> 0) and row (r: heights are
  * at most 2^27 < p) as there. A constant >= p is refused as non-canonical.
+ *   Indexed reads: node kind 22, `at`, is the "INDEXED READS" paragraph of include/mstark.h read over this p: the row operand is
+ * the canonical integer in [0, p), compared with the source's height (n, or the input matrix's own height) before anything is
+ * addressed, and a row from the height on reads 0. A program of this configuration is one group: an `at` of a main column that
+ * any step assigns is refused. The same refusals as there.
  *   inputs: an ms_dev_matrix as for msbb_witness_create_device - elem_bytes 1, 2 or 4 - of width n_inputs and a height in
  * [0, n]; rows at or beyond its height read 0. A 4-byte element >= p is refused, naming the first offender in row-major order
  * ("non-canonical input value: row 5, column 1").

@@ -11,6 +11,8 @@
 //   - the slot file [slot][lane] takes 4 bytes per word: in LDS at 256 lanes up to 64 slots, 128 up to 128, 64 up to 256, and in
 //     a global scratch walked in row batches beyond. No barrier: every lane owns its column of the file;
 //   - inputs pass through ingest_babybear into a column-major Montgomery temporary with leading dimension h_in;
+//   - an indexed read (OP_AT) of row i is buf[c * ld + i] with the source's own leading dimension, one scattered 4-byte load
+//     guarded by the source's height (n, or h_in for inputs): a row from the height on loads nothing and reads 0;
 //   - the witness holds no lookup values, so there is nothing beside the assigned columns to update.
 //
 // Order on the context's stream: program upload, [wait for the producer's stream, ingest of the inputs with the offender word,
@@ -64,6 +66,15 @@ __global__ __launch_bounds__(256) void bb_fill_k(BflParams p) {
           v = bb_from_monty(p.pre[ins.w * p.pre_ld + row]);
         else
           v = row < p.h_in ? bb_from_monty(p.inp[ins.w * p.h_in + row]) : 0;
+        break;
+      }
+      case OP_AT: {  // [row slot, source | column << 8]: the bound check is the definition, a row from the height on loads nothing
+        const size_t i = slots[ins.z * stride];
+        const u32 src = ins.w & 0xff;
+        const size_t col = ins.w >> 8;
+        v = 0;
+        if (i < (src == FL_SRC_INPUT ? p.h_in : p.n))
+          v = bb_from_monty(src == FL_SRC_MAIN ? p.trace[col * p.ld + i] : src == FL_SRC_PRE ? p.pre[col * p.pre_ld + i] : p.inp[col * p.h_in + i]);
         break;
       }
       case OP_ROW: v = (u32)r; break;  // (heights are at most 2^27 < p)

@@ -10,8 +10,9 @@
 // Device side: fill_k, one thread per row. The slot file is [slot][lane] - in LDS at 256 / 128 / 64 lanes per workgroup (lane l
 // touches the 8-byte words slot * lanes + l: consecutive lanes, consecutive words, no bank conflict), or, when it does not fit
 // 64 KB at 64 lanes, in a global scratch walked in row batches (tiers 1 and 4 of check_dev.h, by the placement rules of
-// msamd.h). Rows are independent: offset-1 reads of the main trace are refused for every column the program assigns, so no
-// thread reads what another one writes.
+// msamd.h). Rows are independent: offset-1 reads of the main trace, and reads of it at a computed row (OP_AT, "INDEXED READS"),
+// are refused for every column the program assigns, so no thread reads what another one writes. An indexed read is one scattered
+// 8-byte load of trace, preprocessed trace or inputs, guarded by the source's height: a row from the height on loads nothing.
 //
 // Order on the context's stream: program upload, [wait for the producer's stream, ingest of the inputs into a row-major
 // temporary with the offender word, ONE host wait for that word], fill_k, lookup_values_k when the witness holds lookup values
@@ -82,6 +83,17 @@ __global__ __launch_bounds__(256) void fill_k(FlParams p) {
           v = p.pre[row * p.pre_w + ins.w];
         else
           v = row < p.h_in ? p.inp[row * p.n_in + ins.w] : 0;
+        break;
+      }
+      case OP_AT: {  // [row slot, source | column << 8]: the bound check is the definition, a row from the height on loads nothing
+        const u64 i = slots[ins.z * stride];
+        const u32 src = ins.w & 0xff;
+        const size_t col = ins.w >> 8;
+        v = 0;
+        if (i < (u64)(src == FL_SRC_INPUT ? p.h_in : p.n)) {
+          const size_t row = (size_t)i;
+          v = src == FL_SRC_MAIN ? p.trace[row * p.main_w + col] : src == FL_SRC_PRE ? p.pre[row * p.pre_w + col] : p.inp[row * p.n_in + col];
+        }
         break;
       }
       case OP_ROW: v = (u64)r; break;

@@ -16,6 +16,12 @@
 // COEFFICIENT PASS over its two roots (mul, add), or over the add root alone when the mul root is the constant 1: a pseudo-group
 // whose outputs 0 / 1 go to a temporary instead of the trace and bind no column. A read of a column that an earlier group
 // assigned is an ordinary load of the trace, which that group has finished by then.
+//
+// An INDEXED READ (kind 22, `at`: column c of a source at the row that another node computes) is an instance with ONE operand,
+// the row, and an immediate, source | column << 8; it is hash-consed on both, so equal reads are issued once. It never resolves
+// to an assignment of its group - the group rule refuses an `at` of a main column that the same or a later group assigns - and
+// so it follows the group's assignments (`deps`) through its row operand alone. Its instruction word is
+// [OP_AT, dst slot, row slot, source | column << 8]: a column is below 2^20, so the immediate takes 28 bits.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -42,7 +48,7 @@ constexpr FillField FILL_BABYBEAR{0x3130424C49464D00ull, 0x78000001ull, 32, 0}; 
 constexpr uint32_t FL_NONE = ~0u;
 constexpr uint32_t FL_SRC_PRE = 0, FL_SRC_MAIN = 1, FL_SRC_INPUT = 3;
 constexpr size_t FL_MAX_WIDTH = size_t(1) << 20, FL_MAX_NODES = size_t(1) << 24;
-enum : uint32_t { OP_ROW = 16, OP_BITS, OP_INV0, OP_LT, OP_XOR, OP_AND };  // behind the kinds of program.h
+enum : uint32_t { OP_ROW = 16, OP_BITS, OP_INV0, OP_LT, OP_XOR, OP_AND, OP_AT };  // behind the kinds of program.h
 
 struct FillPass {  // what one launch of the fill kernel runs
   size_t n_instr = 0, n_slots = 0;
@@ -108,7 +114,7 @@ inline FillPass fill_linearise(const std::vector<PNode>& nodes, const std::vecto
         stack.push_back((uint32_t)n.a);
         continue;
       }
-      if (bin && !ready(n.b)) {
+      if ((bin || n.kind == OP_AT) && !ready(n.b)) {  // (the row operand of an indexed read is its b)
         stack.push_back((uint32_t)n.b);
         continue;
       }
@@ -119,6 +125,8 @@ inline FillPass fill_linearise(const std::vector<PNode>& nodes, const std::vecto
         id = bind && deps[i] && binding[n.a] != FL_NONE ? binding[n.a] : intern(OP_VAR, n.source | (n.offset << 8), (uint32_t)n.a, 0);
       else if (n.kind == OP_ROW)
         id = intern(OP_ROW, 0, 0, 0);
+      else if (n.kind == OP_AT)
+        id = intern(OP_AT, inst_of[n.b], n.source | ((uint32_t)n.a << 8), 0);
       else if (un)
         id = intern(n.kind, inst_of[n.a], n.kind == OP_BITS ? (uint32_t)n.b : 0, 0);
       else
@@ -141,7 +149,7 @@ inline FillPass fill_linearise(const std::vector<PNode>& nodes, const std::vecto
       needed[binding[m]] = 1;
       last_use[binding[m]] = INF;
     }
-  auto has_a = [](uint32_t op) { return fl_unary(op) || fl_binary(op); };
+  auto has_a = [](uint32_t op) { return fl_unary(op) || fl_binary(op) || op == OP_AT; };  // (OP_AT: a is the row instance, b the immediate)
   for (size_t i = NI; i-- > 0;) {
     if (!needed[i]) continue;
     auto use = [&](uint32_t c) {
@@ -258,6 +266,18 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
       if (!v2 && n.source == FL_SRC_MAIN && n.offset == 1 && assigned[n.a])  // (the second format: by groups, below)
         fail(at + "offset-1 read of main column " + std::to_string(n.a) + ", which the program assigns (the next row may be read only of columns no step assigns)");
       deps[i] = n.source == FL_SRC_MAIN && n.offset == 0;
+    } else if (n.kind == OP_AT) {
+      if (n.source == 2) fail(at + "stage-2 columns are not allowed in a fill program");
+      if (n.source != FL_SRC_PRE && n.source != FL_SRC_MAIN && n.source != FL_SRC_INPUT) fail(at + "unknown source of an indexed read");
+      const u64 width = n.source == FL_SRC_PRE ? pre_w : n.source == FL_SRC_MAIN ? main_w : n_in;
+      if (n.offset) fail(at + "the offset field of an indexed read must be 0");
+      if (n.a >= width)
+        fail(at + "indexed read of column " + std::to_string(n.a) + " of source " + std::to_string(n.source) + ", which is out of range (width " + std::to_string(width) + ")");
+      if (n.b >= i) fail(at + "forward row operand");
+      if (!v2 && n.source == FL_SRC_MAIN && assigned[n.a])  // (one group; the second format: by groups, below)
+        fail(at + "indexed read of main column " + std::to_string(n.a) +
+             " by step group 0, which step group 0 assigns (a computed row may be read only of columns that no step of the same or a later group assigns)");
+      deps[i] = deps[n.b];
     } else if (n.kind == OP_PUBLIC) {
       fail(at + "publics are not allowed in a fill program");
     } else if (n.kind == OP_IS_FIRST || n.kind == OP_IS_LAST || n.kind == OP_IS_TRANS) {
@@ -303,7 +323,8 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
     at_step = sc.step + 1;
   }
   if (ns > at_step) ranges.push_back(Range{at_step, (size_t)ns, nullptr});
-  // the offset-1 rule: group g may read the next row of main column m only if no step of group g or of a later group assigns m
+  // the offset-1 rule: group g may read the next row of main column m, or m at a computed row, only if no step of group g or of
+  // a later group assigns m
   const uint32_t NG = (uint32_t)ranges.size();
   std::vector<uint32_t> last_group(main_w, FL_NONE);  // the last group that assigns the column
   for (uint32_t g = 0; g < NG; g++)
@@ -320,7 +341,10 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
       seen[i] = g;
       const PNode& n = nodes[i];
       if (fl_unary(n.kind) || fl_binary(n.kind)) stack.push_back((uint32_t)n.a);
-      if (fl_binary(n.kind)) stack.push_back((uint32_t)n.b);
+      if (fl_binary(n.kind) || n.kind == OP_AT) stack.push_back((uint32_t)n.b);
+      if (n.kind == OP_AT && n.source == FL_SRC_MAIN && last_group[n.a] != FL_NONE && last_group[n.a] >= g)  // (a scan's own dst is such a column)
+        fail("node " + std::to_string(i) + ": indexed read of main column " + std::to_string(n.a) + " by step group " + std::to_string(g) +
+             ", which step group " + std::to_string(last_group[n.a]) + " assigns (a computed row may be read only of columns that no step of the same or a later group assigns)");
       if (n.kind != OP_VAR || n.source != FL_SRC_MAIN) continue;
       if (rg.scan && n.a == steps[rg.lo].first)
         fail("step " + std::to_string(rg.lo) + ": the coefficients of a scan step read its own dst, main column " + std::to_string(n.a) + " at offset " +

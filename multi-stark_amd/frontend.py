@@ -27,6 +27,7 @@ SRC_PRE, SRC_MAIN, SRC_STAGE2 = 0, 1, 2
 BLOB_MAGIC = 0x31305359534D0000
 # witness-only node kinds and the input source of fill programs (compile_fill, ms_witness_fill): never part of a constraint
 N_ROW, N_BITS, N_INV0, N_LT, N_XOR, N_AND = range(16, 22)
+N_AT = 22  # an indexed read: column a of `source` at the row that node b computes (Expr.main_at / pre_at / input_at)
 SRC_INPUT = 3
 FILL_MAGIC = 0x31304C4C49464D00  # "\0MFILL01"; over BabyBear "\0MFILB01": a fill program belongs to the field its constants were folded in
 FILL_BITS = 64  # bits(x, lo, length) needs lo + length <= the width of a value: 64, over BabyBear 32
@@ -96,6 +97,23 @@ class Expr:
     @staticmethod
     def row():
         return Expr(N_ROW)
+
+    # indexed reads: column c at the row that `row` (a fill expression or an integer) computes; 0 from the source's height on
+    @staticmethod
+    def at(source, c, row):
+        return Expr(N_AT, int(c), Expr.lift(row), source, 0)
+
+    @staticmethod
+    def main_at(c, row):
+        return Expr.at(SRC_MAIN, c, row)
+
+    @staticmethod
+    def pre_at(c, row):
+        return Expr.at(SRC_PRE, c, row)
+
+    @staticmethod
+    def input_at(c, row):
+        return Expr.at(SRC_INPUT, c, row)
 
     def is_const(self, v=None):
         return self.kind == N_CONST and (v is None or self.a == v % P)
@@ -295,7 +313,7 @@ class _Interner:
     def compile_expr(self, e, spec, allow_stage2):
         k = e.kind
         if k >= N_ROW or (k == N_VAR and e.source == SRC_INPUT):
-            raise CompileError("WitnessOnlyNode kind=%d: row, bits, inv0, lt, bit_xor, bit_and and inputs belong to fill programs" % k)
+            raise CompileError("WitnessOnlyNode kind=%d: row, bits, inv0, lt, bit_xor, bit_and, indexed reads and inputs belong to fill programs" % k)
         if k == N_CONST:
             return self.constant(e.a)
         if k == N_VAR:
@@ -563,7 +581,8 @@ def system_blob(params, compiled, poseidon2=None):
 
 # --------------------------------------------------------------------------- fill programs (ms_witness_fill)
 # How the dependent columns of one circuit follow from inputs and other columns: an ordered list of steps (dst_column, Expr)
-# over the constraint algebra plus the witness-only leaves Expr.input / Expr.input_next / Expr.row and the operators below.
+# over the constraint algebra plus the witness-only leaves Expr.input / Expr.input_next / Expr.row, the indexed reads
+# Expr.main_at / Expr.pre_at / Expr.input_at (a column at a computed row; 0 from the source's height on) and the operators below.
 # The semantics are written down in include/mstark.h; operands are the canonical integers in [0, P).
 def bits(x, lo, length):
     """(x >> lo) & (2^length - 1), 1 <= length, lo + length <= 64 (32 under field(BABYBEAR))"""
@@ -644,6 +663,15 @@ class _FillInterner(_Interner):
                                "(flags come from row, lt and inv0)" % k)
         if k == N_ROW:
             return self.intern((N_ROW, 0, 0, 0, 0))
+        if k == N_AT:
+            if e.source not in (SRC_PRE, SRC_MAIN, SRC_INPUT):
+                raise CompileError("Stage2InFillProgram")
+            width = {SRC_PRE: spec["preprocessed_width"], SRC_MAIN: spec["main_width"], SRC_INPUT: spec["n_inputs"]}[e.source]
+            if e.offset:
+                raise CompileError("RowOffsetOutOfRange offset=%d: an indexed read has no row offset" % e.offset)
+            if not 0 <= e.a < width:
+                raise CompileError("ColumnOutOfRange source=%d index=%d width=%d" % (e.source, e.a, width))
+            return self.intern((N_AT, e.source, 0, e.a, self.compile_fill_expr(e.b, spec)))  # (a constant row stays a node)
         if k not in (N_ADD, N_SUB, N_MUL, N_NEG, N_BITS, N_INV0, N_LT, N_XOR, N_AND):
             raise CompileError("UnknownNodeKind kind=%d" % k)
         a = self.compile_fill_expr(e.a, spec)
@@ -714,18 +742,23 @@ class FillProgram:
 
 
 def _main_reads(nodes):
-    """per node: the main columns it reads, directly or through operands, as (at offset 0, at offset 1)"""
+    """per node: the main columns it reads, directly or through operands, as (at offset 0, at offset 1, at a computed row);
+    for the group rule an indexed read counts as an offset-1 read, and it is kept apart only for the error's name"""
+    none = frozenset()
     reads = []
     for (kind, source, offset, a, b) in nodes:
         if kind == N_VAR:
-            cols = frozenset([a]) if source == SRC_MAIN else frozenset()
-            reads.append((frozenset(), cols) if offset else (cols, frozenset()))
+            cols = frozenset([a]) if source == SRC_MAIN else none
+            reads.append((none, cols, none) if offset else (cols, none, none))
+        elif kind == N_AT:
+            r = reads[b]
+            reads.append((r[0], r[1], r[2] | frozenset([a])) if source == SRC_MAIN else r)
         elif kind in (N_NEG, N_INV0, N_BITS):
             reads.append(reads[a])
         elif kind in (N_ADD, N_SUB, N_MUL, N_LT, N_XOR, N_AND):
-            reads.append((reads[a][0] | reads[b][0], reads[a][1] | reads[b][1]))
+            reads.append(tuple(reads[a][t] | reads[b][t] for t in range(3)))
         else:
-            reads.append((frozenset(), frozenset()))
+            reads.append((none, none, none))
     return reads
 
 
@@ -753,6 +786,12 @@ def compile_fill(main_width, preprocessed_width, n_inputs, steps):
         for (kind, source, offset, a, _) in it.nodes:
             if kind == N_VAR and source == SRC_MAIN and offset == 1 and a in assigned:
                 raise CompileError("NextRowOfAssignedColumn column=%d: a fill program may read the next row only of columns it does not assign" % a)
+        if any(kind == N_AT for (kind, _, _, _, _) in it.nodes):
+            reads = _main_reads(it.nodes)
+            for k, (_, root) in enumerate(out):
+                for m in sorted(reads[root][2] & assigned):
+                    raise CompileError("IndexedReadOfAssignedColumn column=%d step=%d: a computed row may be read only of columns that no step "
+                                       "of the same or a later group assigns (a program without scan steps is one group)" % (m, k))
         return FillProgram(spec["main_width"], spec["preprocessed_width"], spec["n_inputs"], it.nodes, out)
     # groups: a scan step is one, a run of ordinary steps between scans is one
     mul_of = {k: mul for k, mul, _ in scans}
@@ -775,6 +814,10 @@ def compile_fill(main_width, preprocessed_width, n_inputs, steps):
         for m in sorted(at1):
             if last_group.get(m, -1) >= group[k]:
                 raise CompileError("NextRowOfAssignedColumn column=%d step=%d: the next row may be read only of columns that no step of "
+                                   "the same or a later group assigns (group %d reads, group %d assigns)" % (m, k, group[k], last_group[m]))
+        for m in sorted(frozenset().union(*(reads[r][2] for r in roots))):  # (a scan's own dst is such a column)
+            if last_group.get(m, -1) >= group[k]:
+                raise CompileError("IndexedReadOfAssignedColumn column=%d step=%d: a computed row may be read only of columns that no step of "
                                    "the same or a later group assigns (group %d reads, group %d assigns)" % (m, k, group[k], last_group[m]))
     return FillProgram(spec["main_width"], spec["preprocessed_width"], spec["n_inputs"], it.nodes, out, scans)
 
@@ -803,6 +846,29 @@ def u32_add_halves_fill_program(num_adds):
         steps += [(base, bits(lo, 0, 8)), (base + 1, bits(lo, 8, 8)), (base + 2, bits(hi, 0, 8)), (base + 3, bits(hi, 8, 8))]
     steps += [(12, bits(s_hi, 16, 1)), (13, lt(Expr.row(), num_adds))]
     return compile_fill(14, 0, 4, steps)
+
+
+def rows_per_item_fill_program(k):
+    """A circuit that spends k rows on every item (k a power of two, at most 256): row r belongs to item r >> log2(k) and holds
+    limb r & (k - 1) of it. The input matrix has one row per item and max(k / 2, 1) columns of 16-bit words, two 8-bit limbs
+    each (limb j is byte j & 1 of word j >> 1), so the program means the same over both fields. Columns: 0 the item's number,
+    1 the limb's number, 2 the limb - every row of an item reads the item's input row, Expr.input_at(c, item), and the limb is
+    selected by the bits of the limb's number. Rows behind the last item read 0 (an index from the height on)."""
+    k = int(k)
+    log_k = k.bit_length() - 1
+    if k < 1 or k != 1 << log_k or k > 256:
+        raise CompileError("RowsPerItem k=%d: a power of two between 1 and 256" % k)
+    row = Expr.row()
+    item = bits(row, log_k, 32 - log_k)
+    which = bits(row, 0, log_k) if log_k else Expr.const(0)
+    bit = [bits(row, t, 1) for t in range(log_k)]
+    limb = Expr.const(0)
+    for j in range(k):
+        sel = Expr.const(1)
+        for t in range(log_k):
+            sel = sel * (bit[t] if (j >> t) & 1 else 1 - bit[t])
+        limb = limb + sel * bits(Expr.input_at(j >> 1, item), 8 * (j & 1), 8)
+    return compile_fill(3, 0, max(k // 2, 1), [(0, item), (1, which), (2, limb)])
 
 
 # --------------------------------------------------------------------------- circuits

@@ -23,6 +23,14 @@ msbb_witness_fill alone) against the host route, frontend._u32_add_traces (numpy
 the same program without them (the difference is what the scans cost), the running sum alone in the additive form (multiplier
 the constant 1) and in the affine form (multiplier an input column of ones), and the host route the scans replace -
 ms_witness_trace, one sequential loop over the rows, ms_witness_create.
+  python tools/witness_fill.py --gather [--config babybear] [--log-size 20] [--reps 9]
+--gather: the price of an indexed read (frontend.Expr.main_at). A test circuit of 4 columns - a value, the identity index, a
+random permutation, and the column that is written - is filled by three one-step programs in turn: the value through the
+identity index, the value through the permutation, and the ordinary offset-0 copy. None reads inputs, so a call is the program
+upload and one launch of the fill kernel.
+  python tools/witness_fill.py --alone [--log-size 20] [--reps 9]
+--alone: ms_witness_fill of U32Add from the pairs and nothing else in the process: the line by which two builds are compared,
+one process each, in turn.
 Timing: wall time of each route (all return synchronised), alternating after two warm-up rounds; median, minimum and maximum are
 printed. No figure here is a share of peak."""
 import argparse
@@ -43,6 +51,8 @@ ap.add_argument("--config", default="goldilocks", choices=["goldilocks", "babybe
 ap.add_argument("--log-size", type=int, default=20)
 ap.add_argument("--reps", type=int, default=9)
 ap.add_argument("--scan", action="store_true", help="the scan-step leg (Goldilocks)")
+ap.add_argument("--gather", action="store_true", help="the indexed-read leg (both configurations)")
+ap.add_argument("--alone", action="store_true", help="ms_witness_fill of U32Add alone in the process (Goldilocks)")
 args = ap.parse_args()
 
 pkg = load_package()
@@ -213,6 +223,79 @@ def scan_leg():
     state.clear()  # witnesses go before their system
 
 
+def gather_leg():
+    """--gather: what an indexed read costs. One circuit of 4 columns (value, identity index, a random permutation, out); three
+    one-step programs write `out` and alternate: the value through the identity index, through the permutation, and as the
+    ordinary offset-0 copy. No inputs, so no ingest and no host wait: the call is program upload and one launch."""
+    E = fe.Expr
+    bb_cfg = args.config == "babybear"
+    rng = np.random.default_rng(1)
+    if bb_cfg:
+        api = pkg.babybear
+        k = fe.poseidon2_constants()
+        api.set_poseidon2(ctx, k)
+        p = fe.BABYBEAR["P"]
+    else:
+        api, p = pkg, fe.P
+    value = rng.integers(0, p, size=n, dtype=np.uint64)
+    perm = rng.permutation(n).astype(np.uint64)
+    trace = np.stack([value, np.arange(n, dtype=np.uint64), perm, np.zeros(n, dtype=np.uint64)], axis=1)
+    with fe.field(fe.BABYBEAR if bb_cfg else fe.GOLDILOCKS):
+        inputs = [fe.CircuitInputs(4, None, [E.main(3) * E.main(3) - E.main(3)], [], [])]
+        system = api.System.new(ctx, fe.bench_params() if not bb_cfg else fe.test_params(), inputs, *([k] if bb_cfg else []))
+        progs = [("identity index: out = main_at(0, main(1))", fe.compile_fill(4, 0, 0, [(3, E.main_at(0, E.main(1)))]), value),
+                 ("random permutation: out = main_at(0, main(2))", fe.compile_fill(4, 0, 0, [(3, E.main_at(0, E.main(2)))]), value[perm.astype(np.int64)]),
+                 ("ordinary copy: out = main(0)", fe.compile_fill(4, 0, 0, [(3, E.main(0))]), value)]
+        packed = fe.pack_claims([])
+    on_dev = torch.from_numpy(trace.astype(np.uint32).view(np.int32) if bb_cfg else trace.view(np.int64)).cuda()
+    w = system.witness_from_device([on_dev], packed)
+    for name, prog, want in progs:
+        rep = w.fill(0, prog)
+        got = w.trace(0)
+        ok = bool(np.array_equal(got[:, 3].astype(np.uint64), want)) and bool(np.array_equal(got[:, :3].astype(np.uint64), trace[:, :3]))
+        print("%-48s %s; %s; equals numpy: %s" % (name, api.fill_program_info(prog), rep, ok), flush=True)
+        assert ok
+
+    def fill(prog):
+        def run():
+            w.fill(0, prog)
+            ctx.sync()
+        return run
+
+    print("\n# %s, 2^%d rows: the three routes, alternating" % (args.config, args.log_size))
+    times = timed([fill(prog) for _, prog, _ in progs], args.reps)
+    call = "msbb_witness_fill" if bb_cfg else "ms_witness_fill"
+    for (name, _, _), t in zip(progs, times):
+        line("%s, %s" % (call, name.split(":")[0]), t)
+    m = statistics.median
+    print("identity / copy = %.2f, permutation / copy = %.2f, permutation / identity = %.2f" % (
+        m(times[0]) / m(times[2]), m(times[1]) / m(times[2]), m(times[1]) / m(times[0])))
+    del w
+
+
+def alone_leg():
+    """--alone: ms_witness_fill of U32Add from the pairs and nothing else in the process - the figure to compare two builds by"""
+    system = pkg.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs())
+    xs, ys = fe.xorshift_pairs(n)
+    prog = fe.u32_add_fill_program(n)
+    pairs = torch.from_numpy(np.stack([xs, ys], axis=1).astype(np.uint32).view(np.int32)).cuda()
+    w = system.witness_from_device([torch.zeros((256, 1), dtype=torch.int64, device="cuda"), torch.zeros((n, 14), dtype=torch.int64, device="cuda")],
+                                   fe.pack_claims([]))
+
+    def fill_alone():
+        w.fill(1, prog, pairs)
+        ctx.sync()
+
+    line("ms_witness_fill alone", timed([fill_alone], args.reps)[0])
+    del w
+
+
+if args.gather:
+    gather_leg()
+    sys.exit(0)
+if args.alone:
+    alone_leg()
+    sys.exit(0)
 if args.config == "babybear":
     babybear()
     sys.exit(0)
