@@ -209,6 +209,10 @@ extern "C" {
                            producer_stream: *mut c_void, summary: *mut u64) -> i32;
     pub fn ms_fill_program_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
     pub fn ms_fill_scan_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
+    /// what: 0 = MS_SORT_PERM, 1 = MS_SORT_RANK; summary: 4 words
+    pub fn ms_witness_argsort(sys: *mut ms_system, w: *mut ms_witness, circuit: usize, key_columns: *const u32, n_keys: usize,
+                              dst_column: u32, what: u32, summary: *mut u64) -> i32;
+    pub fn ms_sort_info(out4: *mut u64) -> i32;
     pub fn ms_witness_claims_accumulator(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_out: *mut u64) -> i32;
     pub fn ms_stage2_build(w: *mut ms_witness, beta: *const u64, gamma: *const u64, acc_in: *const u64, accs_out: *mut u64,
                            traces_out: *mut *mut ms_trace) -> i32;

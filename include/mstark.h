@@ -456,6 +456,49 @@ int32_t ms_fill_program_info(const uint8_t* program, size_t program_len, uint64_
  * one coefficient pass per scan), scans in the additive form, T = rows per scan tile]. Texts start "ms_fill_scan_info: ". */
 int32_t ms_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
 
+/* ---- The sorting permutation of a circuit's rows, made on the device. Indexed reads let a fill program write a sorted or
+ * permuted copy of a column (sorted[r] = log[perm[r]]); this call produces perm, so that the witness of an offline memory
+ * check, of a range check by sorted differences or of a permutation argument never leaves HBM: sort, gather, scan.
+ * Goldilocks / BLAKE3 configuration.
+ *   Definition. Let n be the circuit's height in the witness and k_0 .. k_{m-1} the key columns, 1 <= m <= 8. Row i comes
+ * before row j iff the tuple (trace[i][k_0], ..., trace[i][k_{m-1}], i) is lexicographically smaller, the cells compared as the
+ * canonical integers in [0, p) that the trace holds: an unsigned 64-bit comparison. The row index is the last component, so the
+ * order is total, the sort is stable and the result is unique. The same column may appear several times among the keys; that
+ * changes nothing.
+ *     what = MS_SORT_PERM   trace[t][dst_column] = the row at sorted position t
+ *     what = MS_SORT_RANK   trace[r][dst_column] = the sorted position of row r (the inverse permutation)
+ * Every cell of dst_column is written once. No other cell of the trace changes, and no other circuit is touched.
+ *   Held lookup values. Where the witness holds lookup values for the circuit they are recomputed by from_stage_1 on the device
+ * inside the same call, as ms_witness_fill does.
+ *   A trace column, not a caller's buffer: nothing in this interface writes caller memory, ms_witness_trace reads the column
+ * back, and no scratch column is needed - the permutation may land in a column that the next fill program overwrites with the
+ * sorted keys. With columns (ADDR, VAL, S_ADDR, S_VAL), in the front end's notation, under the group rule of ms_witness_fill:
+ *     w.argsort(c, [ADDR], dst=S_ADDR)
+ *     w.fill(c, compile_fill(W, 0, 0, [(S_VAL,  E.main_at(VAL,  E.main(S_ADDR))),
+ *                                      (S_ADDR, E.main_at(ADDR, E.main(S_ADDR)))]))
+ *   Execution: a least-significant-digit radix sort over (key, row index) pairs with 8-bit digits, the last key column first,
+ * row indices as u32. One launch per key column counts its eight digit histograms (the one for the last key column also pulls
+ * the column out of the row-major trace), the host reads all of them in one copy and skips every digit in which all n rows
+ * share one value: a byte-valued column costs one pass, a constant column none. Each pass that runs is three launches over
+ * tiles of T rows: per-tile digit counts, exclusive offsets over the digit-major 256 x tiles array by one workgroup in rounds
+ * of R counts, and a scatter that recomputes stable local ranks. No position depends on the order in which atomics land.
+ *   summary: [0] rows  [1] key columns  [2] digit passes run  [3] digit passes skipped ([2] + [3] = 8 x key columns).
+ *   MS_ERR (text via ms_last_error(), starting "ms_witness_argsort: "; each refusal comes before anything is written, the
+ * context stays usable): a witness of another system; a host-resident witness; a witness with circuits held by another rank; a
+ * circuit out of range, inactive or without a trace on this device; n_keys 0 or above 8; a key column or dst_column at or
+ * beyond main_width; dst_column among the keys; what neither 0 nor 1; a height above 2^31; a witness that holds lookup values
+ * for the circuit whose lookup prefix does not fit the device sweep.
+ *   Host waits: exactly one, the copy of the histograms; nothing has been written to the trace by then.
+ *   Temporaries: 24 bytes x n (two key and two index buffers) and 1 KB per tile, next to 8 KB per key column and histogram
+ * workgroup (at most 256 of them). */
+#define MS_SORT_PERM 0
+#define MS_SORT_RANK 1
+int32_t ms_witness_argsort(ms_system* sys, ms_witness* w, size_t circuit, const uint32_t* key_columns, size_t n_keys,
+                           uint32_t dst_column, uint32_t what, uint64_t summary[4]);
+/* Host code, no device: out4 = [T = rows per tile, bits per digit, R = per-tile counts handled per round of the offsets step,
+ * largest n_keys]. */
+int32_t ms_sort_info(uint64_t out4[4]);
+
 /* ---- System::prove_multiple_claims (src/prover.rs:290-603). Writes Proof::to_bytes (src/prover.rs:241-248).
  * stage_ms (optional, 6 doubles): stage1_commit, lookup_construction, stage2_commit, quotient, fri_open, total —
  * the reference's span names (src/prover.rs:336-538). Returns MS_ERR_BUFFER with *proof_len = needed size if

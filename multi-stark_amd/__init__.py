@@ -54,7 +54,7 @@ def exported_symbols():
             "ms_witness_commit_stage1", "ms_challenger_observe_claims", "ms_witness_claims_accumulator", "ms_stage2_build",
             "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes", "ms_witness_check", "ms_system_check_info", "ms_witness_lookup_balance",
             "ms_system_multiplicity_slot", "ms_witness_derive_multiplicities", "ms_witness_fill", "ms_fill_program_info",
-            "ms_fill_scan_info"]
+            "ms_fill_scan_info", "ms_witness_argsort", "ms_sort_info"]
 
 
 # ms_system_circuit_kernels / msbb_system_circuit_kernels (MS_KERNEL_* in include/mstark.h)
@@ -705,8 +705,44 @@ class FillReport:
         return "%d rows x %d steps: %d instructions per row, %s" % (self.rows, self.steps, self.instructions, form)
 
 
+SORT_PERM, SORT_RANK = 0, 1  # MS_SORT_* of include/mstark.h
+
+
+def sort_info():
+    """ms_sort_info (host only) -> (T = rows per tile, bits per digit, R = per-tile counts per round of the offsets step,
+    largest number of key columns) of SystemWitness.argsort"""
+    o = np.zeros(4, dtype=np.uint64)
+    _check(lib().ms_sort_info(_p(o)))
+    return tuple(int(x) for x in o)
+
+
+class SortReport:
+    """What SystemWitness.argsort returns: .rows, .keys (key columns), .passes (digit passes run), .skipped (digit passes in
+    which all rows share one value)"""
+
+    def __init__(self, rows, keys, passes, skipped):
+        self.rows, self.keys, self.passes, self.skipped = rows, keys, passes, skipped
+
+    def fields(self):
+        return (self.rows, self.keys, self.passes, self.skipped)
+
+    def __str__(self):
+        return "%d rows by %d key column%s: %d digit passes run, %d skipped" % (self.rows, self.keys, "" if self.keys == 1 else "s", self.passes, self.skipped)
+
+
 class SystemWitness:
     """Device-resident SystemWitness + claims (ms_witness). Built by `System.witness`."""
+
+    def argsort(self, circuit, keys, dst, rank=False):
+        """ms_witness_argsort: main column `dst` of `circuit` receives the stable permutation that sorts the rows by the key
+        columns `keys` (primary first; cells compared as unsigned integers, ties by row index) - trace[t][dst] = the row at sorted
+        position t - or, with rank=True, its inverse: trace[r][dst] = the position of row r. Made on the device; held lookup
+        values follow. -> SortReport"""
+        k = np.ascontiguousarray(list(keys), dtype=np.uint32)
+        summary = np.zeros(4, dtype=np.uint64)
+        _check(lib().ms_witness_argsort(self.system.h, self.h, C.c_size_t(circuit), k.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(k.size),
+                                        C.c_uint32(dst), C.c_uint32(int(rank)), _p(summary)))  # (False / True are MS_SORT_PERM / MS_SORT_RANK)
+        return SortReport(*(int(x) for x in summary))
 
     def fill(self, circuit, program, inputs=None, stream=None):
         """ms_witness_fill: the columns of `circuit` that `program` (frontend.compile_fill, or its blob) assigns, evaluated on the

@@ -427,6 +427,20 @@ int32_t ms_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t o
   return MS_OK;
   MS_CATCH
 }
+int32_t ms_witness_argsort(ms_system* sys, ms_witness* w, size_t circuit, const uint32_t* key_columns, size_t n_keys, uint32_t dst_column,
+                           uint32_t what, uint64_t summary[4]) {
+  MS_TRY if (!sys || !w || !summary || (!key_columns && n_keys)) throw std::runtime_error("ms_witness_argsort: null argument");
+  HIP_CHECK(hipSetDevice(sys->sys->ctx->device));
+  witness_argsort(*sys->sys, *w->w, circuit, key_columns, n_keys, dst_column, what, summary);
+  return MS_OK;
+  MS_CATCH
+}
+int32_t ms_sort_info(uint64_t out4[4]) {
+  MS_TRY if (!out4) throw std::runtime_error("ms_sort_info: null argument");
+  sort_info(out4);
+  return MS_OK;
+  MS_CATCH
+}
 int32_t ms_system_check_info(const ms_system* sys, size_t ci, uint64_t out4[4]) {
   MS_TRY if (!sys || !out4) throw std::runtime_error("ms_system_check_info: null argument");
   const HSystem& s = *sys->sys;
