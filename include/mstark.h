@@ -87,7 +87,9 @@ int32_t ms_ctx_kernel_stats(ms_ctx* ctx, int32_t kernel_id, uint64_t* launches, 
 int32_t ms_ctx_kernel_units(ms_ctx* ctx, int32_t kernel_id, double* units);
 int32_t ms_ctx_reset_stats(ms_ctx* ctx);
 /* Diagnostics: the nth device allocation from now fails (0 = off). Lets a test check that an error in the middle of a
- * proof leaves the library usable (queued read-backs dropped, pool intact). */
+ * proof leaves the library usable (queued read-backs dropped, pool intact). It serves the calls that make, fill, sort, check
+ * and verify as well: each of them says below what an allocation failure leaves behind - the witness as it was before the
+ * call, or no witness - and the same call may be made again. */
 int32_t ms_ctx_debug_fail_alloc(ms_ctx* ctx, int32_t nth);
 int32_t ms_kernel_count(void);
 const char* ms_kernel_name(int32_t kernel_id);
@@ -124,7 +126,10 @@ int32_t ms_system_circuit_kernels(const ms_system* sys, size_t circuit, uint32_t
 /* ---- SystemWitness (src/system.rs:225-233) + claims. traces[i]: heights[i] x main_width_i row-major (height 0 =
  * inactive circuit). mult[i] / args[i]: the flat LookupValues storage (src/lookup.rs:392-405); pass mult = NULL
  * to have the library run SystemWitness::from_stage_1 (src/system.rs:244-328) on the host. Claims are given as
- * offsets (n_claims + 1) into claim_data. Everything is uploaded once; ms_prove does not consume it. */
+ * offsets (n_claims + 1) into claim_data. Everything is uploaded once; ms_prove does not consume it. After an allocation
+ * failure (MS_ERR) of this or any other call that makes a witness - ms_witness_create_device, ms_witness_u32_add_bench,
+ * ms_witness_blake3_compressions - there is no witness, *out is not written, the caller's buffers are as they were and no
+ * longer read, the context and the system stay usable, and the call may be made again. */
 int32_t ms_witness_create(ms_system* sys, const uint64_t* const* traces, const uint64_t* heights,
                           const uint64_t* const* mult, const uint64_t* const* args, size_t n_claims,
                           const uint64_t* claim_offsets, const uint64_t* claim_data, ms_witness** out);
@@ -242,7 +247,7 @@ void ms_witness_destroy(ms_witness* w);
  * (ms_witness_create_host*: its traces are not in HBM between proofs); a witness with circuits held by another rank; beta or
  * gamma with a coordinate >= p. Accepted: every device-resident witness - ms_witness_create, ms_witness_create_device,
  * ms_witness_u32_add_bench, ms_witness_blake3_compressions. The witness is not changed: ms_prove behind a check writes the bytes
- * it writes without one.
+ * it writes without one. After an allocation failure (MS_ERR) it is unchanged too, and the next check gives the full report.
  *   Host waits: one, for the report (plus those of the claims' upload paths it shares with ms_stage2_build). */
 #define MS_CHECK_CONSTRAINT 0x1u
 #define MS_CHECK_LOOKUPS 0x2u
@@ -285,7 +290,7 @@ int32_t ms_system_check_info(const ms_system* sys, size_t circuit, uint64_t out4
  * trace) has them computed into temporaries of the call; a lookup prefix that does not fit the device sweep is MS_ERR.
  *   Memory: the grouping table takes 40 bytes x cap, cap = the power of two >= max(64, 2 x M), M = claims + sum over the active
  * circuits of height x num_lookups (1.34 GB at 2^20 additions, M = 14 x 2^20), plus M / 8 bytes of marks; an allocation failure
- * is MS_ERR naming the bytes. MSAMD_LB_HASH_BITS=k (diagnostics, read per call) keeps only the low k bits of the hash: with 0
+ * is MS_ERR naming the bytes, leaves the witness unchanged, as the call does, and the call may be made again. MSAMD_LB_HASH_BITS=k (diagnostics, read per call) keeps only the low k bits of the hash: with 0
  * every probe sequence starts at slot 0 - the report is the same, by a longer way.
  *   Host waits: one when the witness is balanced; one more, to fetch entries and tuples, when it is not and entries_cap > 0. */
 #define MS_LB_ENTRY_WORDS 8
@@ -333,7 +338,10 @@ int32_t ms_witness_lookup_balance(ms_witness* w, uint64_t summary[4], uint64_t* 
  * lookup values the witness does not hold and whose lookup prefix does not fit the device sweep.
  *   Memory: the grouping table takes 48 bytes x cap, cap = the power of two >= max(64, 2 x M), M = claims + sum over the active
  * circuits of height x num_lookups (target slots included), plus 8 bytes per target row and M / 8 bytes of marks; lookup values
- * the witness does not hold are computed into temporaries of the call. An allocation failure is MS_ERR naming the bytes.
+ * the witness does not hold are computed into temporaries of the call; the entries and tuples take entries_cap x
+ * MS_LB_ENTRY_WORDS and min(args_cap, entries_cap x the longest tuple) words, unless entries_cap = 0. An allocation failure is
+ * MS_ERR naming the bytes. Every buffer of the call is allocated before the first write: after an allocation failure the traces,
+ * the claims and the held lookup values are as they were before the call, and the same call may be made again.
  * MSAMD_LB_HASH_BITS as for ms_witness_lookup_balance.
  *   Host waits: one, for the summary; one more, to fetch entries and tuples, when something is unserved and entries_cap > 0. */
 /* out3 = [eligibility: 0 eligible, 1 multiplicity is not one main column at offset 0 (optionally negated),
@@ -387,7 +395,10 @@ int32_t ms_witness_derive_multiplicities(ms_witness* w, const ms_mult_target* ta
  * operand, bad bits fields, a non-canonical constant or a refused node kind; an offset-1 read of an assigned column; an input
  * matrix that fails the checks of ms_witness_create_device; an input height above n; n_inputs > 0 with inputs = NULL; an
  * 8-byte input element >= p, naming the first offender in row-major order ("non-canonical input value: row 5, column 1"); a
- * witness that holds lookup values for the circuit whose lookup prefix does not fit the device sweep.
+ * witness that holds lookup values for the circuit whose lookup prefix does not fit the device sweep. An allocation failure is
+ * MS_ERR as well and comes before the first write too - every buffer of the call, for scans and indexed reads included, is
+ * allocated before the first group is launched: the traces, the claims and the held lookup values are as they were before the
+ * call, and the same call may be made again (which matters for a program that reads a column it overwrites).
  *   Host waits: one when the program reads inputs of height > 0 (the offender word, before the first write); none otherwise -
  * the call then only queues work on the context's stream.
  *
@@ -490,7 +501,8 @@ int32_t ms_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t o
  * for the circuit whose lookup prefix does not fit the device sweep.
  *   Host waits: exactly one, the copy of the histograms; nothing has been written to the trace by then.
  *   Temporaries: 24 bytes x n (two key and two index buffers) and 1 KB per tile, next to 8 KB per key column and histogram
- * workgroup (at most 256 of them). */
+ * workgroup (at most 256 of them). An allocation failure is MS_ERR; all of them are allocated before dst_column is written, so
+ * the traces, the claims and the held lookup values are then as they were before the call, and the same call may be made again. */
 #define MS_SORT_PERM 0
 #define MS_SORT_RANK 1
 int32_t ms_witness_argsort(ms_system* sys, ms_witness* w, size_t circuit, const uint32_t* key_columns, size_t n_keys,
@@ -525,7 +537,8 @@ int32_t ms_verify(ms_system* sys, size_t n_claims, const uint64_t* claim_offsets
  * proofs of work, the arity schedule and the constraints at zeta; the per-query arithmetic (reduced openings, FRI fold
  * chain, final polynomial) and every Merkle path of the batch run on the device in two launches, with one host wait per
  * call (per 256 MB of openings) when the claims stay below 8192 transcript words. MS_ERR for a system whose traces of one
- * kind are together wider than 8192 columns (one leaf is hashed inside a thread). */
+ * kind are together wider than 8192 columns (one leaf is hashed inside a thread). An allocation failure is MS_ERR with the
+ * verdicts unspecified; the same call made again gives them all. */
 int32_t ms_verify_batch(ms_system* sys, size_t n_proofs, const uint64_t* n_claims, const uint64_t* const* claim_offsets,
                         const uint64_t* const* claim_data, const uint8_t* const* proofs, const uint64_t* proof_lens,
                         int32_t* verdicts);

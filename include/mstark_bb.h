@@ -59,7 +59,9 @@ int32_t msbb_witness_create_host(msbb_system* sys, const uint32_t* const* traces
 /* ms_witness_create_device for this configuration: the traces lie in device memory as ms_dev_matrix views (include/mstark.h)
  * with elem_bytes 1, 2 or 4; a 4-byte value >= p is refused with its circuit, row and column; the library's copy is the
  * column-major Montgomery matrix msbb_witness_create would have made. Same copy semantics, producer_stream ordering, single
- * host wait on the traces' path and host-side refusals. Claims come from host memory, as for msbb_witness_create. */
+ * host wait on the traces' path and host-side refusals. Claims come from host memory, as for msbb_witness_create. After an
+ * allocation failure (MS_ERR) of this call or of msbb_witness_create there is no witness, nothing queued still reads the
+ * caller's buffers, which the call never writes, and the call may be made again. */
 int32_t msbb_witness_create_device(msbb_system* sys, const ms_dev_matrix* traces /* one per circuit */, size_t n_claims,
                                    const uint64_t* claim_offsets, const uint32_t* claim_data, void* producer_stream /* hipStream_t, nullable */,
                                    msbb_witness** out);
@@ -85,7 +87,8 @@ void msbb_witness_destroy(msbb_witness* w);
  *   Misuse (MS_ERR, text via ms_last_error(), the context stays usable): a host-resident witness (msbb_witness_create_host); a
  * coordinate of beta or gamma >= p; a null argument. Accepted: msbb_witness_create, msbb_witness_create_device. The witness is
  * not changed: msbb_prove behind a check writes the bytes it writes without one. Host waits: one per call, for the report
- * (the first check of a circuit also builds its check program). */
+ * (the first check of a circuit also builds its check program). After an allocation failure (MS_ERR) the witness is unchanged
+ * and no half-built check program is kept: the next check builds it again and gives the full report. */
 #define MSBB_CHECK_CIRCUIT_WORDS 12
 int32_t msbb_witness_check(msbb_witness* w, const uint32_t beta[4], const uint32_t gamma[4], uint32_t* verdict,
                            uint64_t* circuits /* n_circuits x MSBB_CHECK_CIRCUIT_WORDS */, uint64_t* root_counts /* nullable */,
@@ -116,7 +119,7 @@ int32_t msbb_system_check_info(const msbb_system* sys, size_t circuit, uint64_t 
  * 4 x height x (num_lookups + args_width) bytes, plus 4 x height x lookup prefix length of scratch while its sweep runs; the
  * grouping table takes 32 bytes x cap, cap = the power of two >= max(64, 2 x M), M = claims + sum over the active circuits of
  * height x num_lookups (134 MB for MulAir at 2^20 rows, M = 2^21), plus M / 8 bytes of marks. An allocation failure is MS_ERR
- * naming the bytes. MSAMD_LB_HASH_BITS=k (diagnostics, read per call) keeps only the low k bits of the hash, as for
+ * naming the bytes; the witness is unchanged by it, as by the call, and the call may be made again. MSAMD_LB_HASH_BITS=k (diagnostics, read per call) keeps only the low k bits of the hash, as for
  * ms_witness_lookup_balance: the report is the same, by a longer way.
  *   Host waits: one when the witness is balanced; one more, to fetch entries and tuples, when it is not and entries_cap > 0. */
 int32_t msbb_witness_lookup_balance(msbb_witness* w, uint64_t summary[4], uint64_t* entries, size_t entries_cap /* nullable with cap 0 */,
@@ -144,8 +147,10 @@ int32_t msbb_witness_lookup_balance(msbb_witness* w, uint64_t summary[4], uint64
  * capacity; a target that is out of range, not eligible, or that shares its derived column with an earlier target.
  *   Memory: the grouping table takes 40 bytes x cap, cap = the power of two >= max(64, 2 x M), M = claims + sum over the active
  * circuits of height x num_lookups (target slots included) - the four arrays of the balance and one word per slot for the
- * provider - plus 8 bytes per target row, M / 8 bytes of marks and the sweep temporaries of msbb_witness_lookup_balance. An
- * allocation failure is MS_ERR naming the bytes. MSAMD_LB_HASH_BITS as for msbb_witness_lookup_balance.
+ * provider - plus 8 bytes per target row, M / 8 bytes of marks, the sweep temporaries of msbb_witness_lookup_balance and, unless
+ * entries_cap = 0, the entries and tuples at the caller's capacities. An allocation failure is MS_ERR naming the bytes; every
+ * buffer is allocated before the first write, so the traces and the claims are then as they were before the call, and the same
+ * call may be made again. MSAMD_LB_HASH_BITS as for msbb_witness_lookup_balance.
  *   Host waits: one, for the summary; one more, to fetch entries and tuples, when something is unserved and entries_cap > 0. */
 /* the three numbers of ms_system_multiplicity_slot: [eligibility, column m, sign: 0 push, 1 pull]; one classifier serves both
  * configurations, as it reads the node program only */
@@ -188,7 +193,8 @@ int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target
  * widths other than the circuit's, a dst or a variable out of range, a forward operand, bad bits fields, a non-canonical
  * constant or a refused node kind; an offset-1 read of an assigned column; an input matrix that fails the checks of
  * msbb_witness_create_device (8-byte elements among them); an input height above n; n_inputs > 0 with inputs = NULL; a
- * non-canonical input element; a null w, program or summary.
+ * non-canonical input element; a null w, program or summary. An allocation failure is MS_ERR as well and comes before the
+ * first write too: the witness is as it was before the call, and the same call may be made again.
  *   Host waits: one when the program reads inputs of height > 0 (the offender word, before the first write); none otherwise. */
 int32_t msbb_witness_fill(msbb_witness* w, size_t circuit, const uint8_t* program, size_t program_len,
                           const ms_dev_matrix* inputs /* nullable with n_inputs 0 */, void* producer_stream /* hipStream_t, nullable */,
@@ -217,7 +223,8 @@ int32_t msbb_verify(msbb_system* sys, size_t n_claims, const uint64_t* claim_off
  * bytes can make the call fail or fault: a malformed proof is a verdict. Per proof the host parses, checks the shape, replays
  * the duplex transcript, checks both proofs of work, the arity schedule and the constraints at zeta; the per-query
  * arithmetic (reduced openings, FRI fold chain, final polynomial) and every Merkle path of the batch run on the device in
- * two launches, with one host wait per call (per 256 MB of openings). */
+ * two launches, with one host wait per call (per 256 MB of openings). An allocation failure is MS_ERR with the verdicts
+ * unspecified; the same call made again gives them all. */
 int32_t msbb_verify_batch(msbb_system* sys, size_t n_proofs, const uint64_t* n_claims, const uint64_t* const* claim_offsets,
                           const uint32_t* const* claim_data, const uint8_t* const* proofs, const uint64_t* proof_lens,
                           int32_t* verdicts);

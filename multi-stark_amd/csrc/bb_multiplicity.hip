@@ -228,6 +228,16 @@ void witness_derive_multiplicities(BSystem& sys, BWitness& wit, const ms_mult_ta
   DBuf<u32> wg_counts = bl_alloc<u32>(ctx, n_blocks, DM_CALL, "its per-workgroup counts");
   DBuf<BlSrc> d_srcs = bl_alloc<BlSrc>(ctx, srcs.size(), DM_CALL, "its source table");
   DBuf<DmTgt> d_tg = bl_alloc<DmTgt>(ctx, std::max<size_t>(tg.size(), 1), DM_CALL, "its target table");
+  // the buffers of the second phase, at the caller's capacities: no allocation may follow the first write to the witness (dm_zero_k and
+  // dm_write_k), so that an allocation failure leaves it as it was
+  for (auto& cl : wit.claims) max_len = std::max(max_len, cl.size());
+  const size_t args_room = std::min(args_out ? args_cap : 0, entries_cap * max_len);
+  DBuf<u64> d_entries;
+  DBuf<u32> d_args;
+  if (entries_cap) {
+    d_entries = bl_alloc<u64>(ctx, entries_cap * MS_LB_ENTRY_WORDS, DM_CALL, "its entries");
+    d_args = bl_alloc<u32>(ctx, std::max<size_t>(args_room, 1), DM_CALL, "its tuples");
+  }
   ctx.h2d(d_srcs.p, srcs.data(), srcs.size() * sizeof(BlSrc));
   if (!tg.empty()) ctx.h2d(d_tg.p, tg.data(), tg.size() * sizeof(DmTgt));
   BlTab t;
@@ -258,10 +268,7 @@ void witness_derive_multiplicities(BSystem& sys, BWitness& wit, const ms_mult_ta
   if (!n_out) return;
 
   // some demand is unserved: its first n_out groups, in origin order, and their tuples - the second host wait
-  for (auto& cl : wit.claims) max_len = std::max(max_len, cl.size());
-  const size_t n_args = std::min(args_out ? args_cap : 0, n_out * max_len);
-  DBuf<u64> d_entries = bl_alloc<u64>(ctx, n_out * MS_LB_ENTRY_WORDS, DM_CALL, "its entries");
-  DBuf<u32> d_args = bl_alloc<u32>(ctx, std::max<size_t>(n_args, 1), DM_CALL, "its tuples");
+  const size_t n_args = std::min(args_out ? args_cap : 0, n_out * max_len);  // (<= args_room: n_out <= entries_cap)
   HIP_CHECK(hipMemsetAsync(d_args.p, 0, std::max<size_t>(n_args, 1) * 4, ctx.stream));
   HIP_CHECK(hipMemsetAsync(d_entries.p, 0, n_out * MS_LB_ENTRY_WORDS * 8, ctx.stream));  // (bl_args_k reads every entry, written or not)
   hipLaunchKernelGGL(bl_scan_k, dim3(1), dim3(BL_T), 0, ctx.stream, wg_counts.p, wg_prefix.p, n_blocks);

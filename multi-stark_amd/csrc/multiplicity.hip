@@ -221,6 +221,15 @@ void witness_derive_multiplicities(HSystem& sys, HWitness& wit, const ms_mult_ta
   DBuf<u32> wg_counts(ctx, n_blocks);
   DBuf<LbSrc> d_srcs(ctx, srcs.size());
   DBuf<DmTgt> d_tg(ctx, std::max<size_t>(tg.size(), 1));
+  // the buffers of the second phase, at the caller's capacities: no allocation may follow the first write to the witness (dm_zero_k), so that
+  // an allocation failure leaves it as it was
+  for (size_t i = 0; i < n_claims; i++) max_len = std::max<size_t>(max_len, wit.claim_offsets[i + 1] - wit.claim_offsets[i]);
+  const size_t args_room = std::min(args_out ? args_cap : 0, entries_cap * max_len);
+  DBuf<u64> d_entries, d_args;
+  if (entries_cap) {
+    d_entries = lb_alloc(ctx, entries_cap * MS_LB_ENTRY_WORDS, DM_CALL, "its entries");
+    d_args = lb_alloc(ctx, std::max<size_t>(args_room, 1), DM_CALL, "its tuples");
+  }
   ctx.h2d(d_srcs.p, srcs.data(), srcs.size() * sizeof(LbSrc));
   if (!tg.empty()) ctx.h2d(d_tg.p, tg.data(), tg.size() * sizeof(DmTgt));
   LbTab t;
@@ -251,9 +260,7 @@ void witness_derive_multiplicities(HSystem& sys, HWitness& wit, const ms_mult_ta
   if (!n_out) return;
 
   // some demand is unserved: its first n_out groups, in origin order, and their tuples - the second host wait
-  for (size_t i = 0; i < n_claims; i++) max_len = std::max<size_t>(max_len, wit.claim_offsets[i + 1] - wit.claim_offsets[i]);
-  const size_t n_args = std::min(args_out ? args_cap : 0, n_out * max_len);
-  DBuf<u64> d_entries(ctx, n_out * MS_LB_ENTRY_WORDS), d_args(ctx, std::max<size_t>(n_args, 1));
+  const size_t n_args = std::min(args_out ? args_cap : 0, n_out * max_len);  // (<= args_room: n_out <= entries_cap)
   HIP_CHECK(hipMemsetAsync(d_args.p, 0, std::max<size_t>(n_args, 1) * 8, ctx.stream));
   HIP_CHECK(hipMemsetAsync(d_entries.p, 0, n_out * MS_LB_ENTRY_WORDS * 8, ctx.stream));  // (lb_args_k reads every entry, written or not)
   hipLaunchKernelGGL(lb_scan_k, dim3(1), dim3(LB_T), 0, ctx.stream, wg_counts.p, wg_prefix.p, n_blocks);
