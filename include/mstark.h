@@ -470,7 +470,7 @@ int32_t ms_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t o
 /* ---- The sorting permutation of a circuit's rows, made on the device. Indexed reads let a fill program write a sorted or
  * permuted copy of a column (sorted[r] = log[perm[r]]); this call produces perm, so that the witness of an offline memory
  * check, of a range check by sorted differences or of a permutation argument never leaves HBM: sort, gather, scan.
- * Goldilocks / BLAKE3 configuration.
+ * Goldilocks / BLAKE3 configuration; msbb_witness_argsort (include/mstark_bb.h) is the call of the other one.
  *   Definition. Let n be the circuit's height in the witness and k_0 .. k_{m-1} the key columns, 1 <= m <= 8. Row i comes
  * before row j iff the tuple (trace[i][k_0], ..., trace[i][k_{m-1}], i) is lexicographically smaller, the cells compared as the
  * canonical integers in [0, p) that the trace holds: an unsigned 64-bit comparison. The row index is the last component, so the

@@ -204,6 +204,41 @@ int32_t msbb_witness_fill(msbb_witness* w, size_t circuit, const uint8_t* progra
  * columns]. Texts start "msbb_fill_program_info: ". */
 int32_t msbb_fill_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
 
+/* ---- The sorting permutation of a circuit's rows, made on the device: ms_witness_argsort (include/mstark.h, "The sorting
+ * permutation of a circuit's rows") for this configuration, its definition read over p = 2^31 - 2^27 + 1: row i comes before
+ * row j iff (trace[i][k_0], ..., trace[i][k_{m-1}], i) is lexicographically smaller, 1 <= m <= 8, a column may repeat among the
+ * keys, ties go by row index, MS_SORT_PERM / MS_SORT_RANK as there. With msbb_witness_fill's indexed reads behind it a sorted
+ * copy of a column - a memory log in address order, a range check by sorted differences - is made without leaving HBM: sort,
+ * then gather. What differs from the Goldilocks call:
+ *   The system comes from the witness, as for msbb_witness_fill.
+ *   Order: cells are compared as the CANONICAL integers in [0, p), not as the Montgomery words that lie in memory (whose order
+ * is another one).
+ *   Storage: the library's copy of a trace is a column-major matrix of Montgomery words. Every cell of dst_column is written
+ * once, as the Montgomery word of a row index or a position; heights are at most 2^27 < p, so each is a canonical value and
+ * msbb_witness_trace shows it as it is. No other cell, circuit or claim changes.
+ *   No held lookup values: a witness of this configuration holds none, so nothing follows the column.
+ *   Execution: the radix sort of ms_witness_argsort over canonical 32-bit keys - FOUR 8-bit digits per key column. One launch
+ * per key column reads the column (contiguous), converts and counts its four digit histograms; the host reads all of them in one
+ * copy and skips every digit in which all n rows share one value; each pass that runs is the same three launches over tiles of
+ * T rows, with keys and row indices in separate 4-byte buffers: 20 bytes per row and pass where the other call moves 32.
+ *   summary: [0] rows  [1] key columns  [2] digit passes run  [3] digit passes skipped ([2] + [3] = 4 x key columns).
+ *   MS_ERR (text via ms_last_error(), starting "msbb_witness_argsort: "; each refusal comes before anything is written, the
+ * context stays usable): a null w or summary, or null key_columns with n_keys > 0; a host-resident witness; a witness that does
+ * not belong to its system; a circuit out of range, inactive or without a trace on this device; n_keys 0 or above 8; a key
+ * column or dst_column at or beyond main_width; dst_column among the keys; what neither 0 nor 1. A height above 2^27 cannot
+ * reach the call: msbb_witness_create, msbb_witness_create_host and msbb_witness_create_device each refuse a trace taller than
+ * the two-adicity of the field allows ("trace too tall for the two-adicity of BabyBear"); the call keeps the check all the same.
+ * An allocation failure is MS_ERR as well; every buffer is allocated before dst_column is written, so the witness is then as it
+ * was before the call, and the same call may be made again.
+ *   Host waits: exactly one, the copy of the histograms; nothing has been written to the trace by then.
+ *   Temporaries: 16 bytes x n (two key and two index buffers) and 1 KB per tile, next to 4 KB per key column and histogram
+ * workgroup (at most 256 of them). */
+int32_t msbb_witness_argsort(msbb_witness* w, size_t circuit, const uint32_t* key_columns, size_t n_keys, uint32_t dst_column,
+                             uint32_t what /* MS_SORT_PERM, MS_SORT_RANK */, uint64_t summary[4]);
+/* Host code, no device: out4 = [T = rows per tile, bits per digit, R = per-tile counts handled per round of the offsets step,
+ * largest n_keys]. */
+int32_t msbb_sort_info(uint64_t out4[4]);
+
 /* Diagnostics, as ms_witness_trace: one stage-1 trace of a device-resident witness read back, height x main_width, row-major,
  * canonical u32. MS_ERR_BUFFER with *n_words = the needed size; an inactive circuit: 0 words, MS_OK. A host-resident witness or
  * an out-of-range circuit: MS_ERR. */

@@ -25,7 +25,7 @@ def exported_symbols():
             "msbb_system_preprocessed_mmcs", "msbb_witness_commit_stage1", "msbb_witness_claims_accumulator", "msbb_stage2_build",
             "msbb_pcs_commit_traces", "msbb_quotient", "msbb_pcs_commit_ldes", "msbb_pcs_open", "msbb_witness_check", "msbb_system_check_info",
             "msbb_witness_lookup_balance", "msbb_system_multiplicity_slot", "msbb_witness_derive_multiplicities", "msbb_witness_trace",
-            "msbb_witness_fill", "msbb_fill_program_info"]
+            "msbb_witness_fill", "msbb_fill_program_info", "msbb_witness_argsort", "msbb_sort_info"]
 
 
 import sys
@@ -81,7 +81,26 @@ def fill_program_info(program):
     return dict(zip(["instructions", "slots", "lds_lanes", "assigned_columns"], (int(x) for x in o)))
 
 
+def sort_info():
+    """msbb_sort_info (host only) -> (T = rows per tile, bits per digit, R = per-tile counts per round of the offsets step,
+    largest number of key columns) of Witness.argsort"""
+    o = np.zeros(4, dtype=np.uint64)
+    _check(_lib().msbb_sort_info(o.ctypes.data_as(u64p)))
+    return tuple(int(x) for x in o)
+
+
 class Witness:
+    def argsort(self, circuit, keys, dst, rank=False):
+        """msbb_witness_argsort: main column `dst` of `circuit` receives the stable permutation that sorts the rows by the key
+        columns `keys` (primary first; cells compared as canonical values, ties by row index) - trace[t][dst] = the row at sorted
+        position t - or, with rank=True, its inverse: trace[r][dst] = the position of row r. Made on the device. -> the
+        package's SortReport (four digit passes per key column, run or skipped)"""
+        k = np.ascontiguousarray(list(keys), dtype=np.uint32)
+        summary = np.zeros(4, dtype=np.uint64)
+        _check(_lib().msbb_witness_argsort(self.h, C.c_size_t(circuit), _p32(k), C.c_size_t(k.size), C.c_uint32(dst), C.c_uint32(int(rank)),
+                                           summary.ctypes.data_as(u64p)))  # (False / True are MS_SORT_PERM / MS_SORT_RANK)
+        return _pkg().SortReport(*(int(x) for x in summary))
+
     def fill(self, circuit, program, inputs=None, stream=None):
         """msbb_witness_fill: the columns of `circuit` that `program` (frontend.compile_fill under field(BABYBEAR), or its blob)
         assigns, evaluated on the device for every row. inputs: None or a 2-D matrix in device memory (torch tensor or

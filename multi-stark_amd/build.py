@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libmstark_hip.so")
 SOURCES = ["ctx.hip", "ntt.hip", "hash.hip", "lookup.hip", "quotient.hip", "quotient_jit.hip", "check.hip", "balance.hip", "multiplicity.hip", "fill.hip", "argsort.hip", "open.hip", "outer.hip", "prover.hip", "verifier.hip", "verify_dev.hip", "witness_gen.hip", "ingest.hip", "capi.hip",
-           "comm_rccl.hip", "comm_local.hip", "bb_kernels.hip", "bb_check.hip", "bb_balance.hip", "bb_multiplicity.hip", "bb_fill.hip", "bb_verify_dev.hip", "bb_prover.hip", "bb_verifier.hip", "pack_host.cpp"]
+           "comm_rccl.hip", "comm_local.hip", "bb_kernels.hip", "bb_check.hip", "bb_balance.hip", "bb_multiplicity.hip", "bb_fill.hip", "bb_argsort.hip", "bb_verify_dev.hip", "bb_prover.hip", "bb_verifier.hip", "pack_host.cpp"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 

@@ -1584,6 +1584,24 @@ int32_t msbb_fill_program_info(const uint8_t* program, size_t program_len, uint6
   return MS_OK;
   BB_CATCH
 }
+int32_t msbb_witness_argsort(msbb_witness* w, size_t circuit, const uint32_t* key_columns, size_t n_keys, uint32_t dst_column, uint32_t what,
+                             uint64_t summary[4]) {
+  BB_TRY
+  if (!w || !summary || (!key_columns && n_keys)) throw std::runtime_error("msbb_witness_argsort: null argument");
+  BWitness& wit = *w->w;
+  BSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  witness_argsort(sys, wit, circuit, key_columns, n_keys, dst_column, what, summary);
+  return MS_OK;
+  BB_CATCH
+}
+int32_t msbb_sort_info(uint64_t out4[4]) {
+  BB_TRY
+  if (!out4) throw std::runtime_error("msbb_sort_info: null argument");
+  sort_info(out4);
+  return MS_OK;
+  BB_CATCH
+}
 int32_t msbb_witness_trace(msbb_witness* w, size_t circuit, uint32_t* out, size_t cap_words, size_t* n_words) {
   BB_TRY
   if (!w || !n_words) throw std::runtime_error("msbb_witness_trace: null argument");
