@@ -292,11 +292,12 @@ def test_argsort(pkg, fe, actx, oracle, tiles, keys, route):
 
 
 # ---------------------------------------------------------------- c. derive_multiplicities, both fields
-# The device allocations of witness_derive_multiplicities. csrc/multiplicity.hip: table (l. 218), slot_of (l. 219), rep, marks and
-# wg_prefix (l. 220), wg_counts (l. 221), d_srcs (l. 222), d_tg (l. 223) and, with room for entries, d_entries and d_args
-# (l. 230-231) - all before dm_zero_k, the first write to the witness. In front of them lb_sources (csrc/lb_dev.h, l. 346-347)
-# takes two temporaries per circuit with lookups whose values the witness does not hold. csrc/bb_multiplicity.hip has the same
-# ten (l. 224-230 and l. 238-239), and bl_sources (csrc/bb_lb_dev.h, l. 358-362) takes three per circuit with lookups.
+# The device allocations of witness_derive_multiplicities, one driver for both fields (dm_derive, csrc/multiplicity_dev.h):
+# table (l. 226, in LbRun::alloc_table, csrc/lb_dev.h, l. 367), slot_of (l. 227), rep, marks, wg_prefix, wg_counts and d_srcs
+# (l. 228, in LbRun::alloc_rest, csrc/lb_dev.h, l. 372-376), d_tg (l. 229) and, with room for entries, d_entries and d_args
+# (l. 237-238) - all before dm_zero_k, the first write to the witness. In front of them GlLookup::sources (csrc/gl_lb.h,
+# l. 108-109) takes two temporaries per circuit with lookups whose values the witness does not hold, and BbLookup::sources
+# (csrc/bb_lb.h, l. 104-108) takes three per circuit with lookups.
 DM_OWN, DM_ENTRIES, DM_PER_CIRCUIT_GL, DM_PER_CIRCUIT_BB = 8, 2, 2, 3
 
 
@@ -449,9 +450,10 @@ def test_bb_witness_check(pkg, actx, witness):
 
 
 # ---------------------------------------------------------------- e. lookup_balance, both fields
-# The device allocations of witness_lookup_balance. csrc/balance.hip: table (l. 97), rep, marks, wg_prefix (l. 99), wg_counts
-# (l. 100), d_srcs (l. 101) and, behind the first host wait and only when some group is unbalanced and there is room for
-# entries, d_entries and d_args (l. 125); lb_sources in front, as for (c). csrc/bb_balance.hip: l. 97-103 and l. 127-128.
+# The device allocations of witness_lookup_balance, one driver for both fields (lb_balance, csrc/balance_dev.h): table (l. 93, in
+# LbRun::alloc_table, csrc/lb_dev.h, l. 367), rep, marks, wg_prefix, wg_counts and d_srcs (l. 94, in LbRun::alloc_rest,
+# csrc/lb_dev.h, l. 372-376) and, behind the first host wait and only when some group is unbalanced and there is room for
+# entries, d_entries and d_args (l. 113-114); the field's sources in front, as for (c).
 LB_OWN, LB_ENTRIES = 6, 2
 
 
