@@ -255,6 +255,7 @@ extern "C" {
     pub fn msbb_witness_fill(w: *mut msbb_witness, circuit: usize, program: *const u8, program_len: usize, inputs: *const ms_dev_matrix,
                              producer_stream: *mut c_void, summary: *mut u64) -> i32;
     pub fn msbb_fill_program_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
+    pub fn msbb_fill_scan_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
     /// what: 0 = MS_SORT_PERM, 1 = MS_SORT_RANK; summary: 4 words
     pub fn msbb_witness_argsort(w: *mut msbb_witness, circuit: usize, key_columns: *const u32, n_keys: usize, dst_column: u32, what: u32,
                                 summary: *mut u64) -> i32;

@@ -174,7 +174,7 @@ int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target
  * at most 2^27 < p) as there. A constant >= p is refused as non-canonical.
  *   Indexed reads: node kind 22, `at`, is the "INDEXED READS" paragraph of include/mstark.h read over this p: the row operand is
  * the canonical integer in [0, p), compared with the source's height (n, or the input matrix's own height) before anything is
- * addressed, and a row from the height on reads 0. A program of this configuration is one group: an `at` of a main column that
+ * addressed, and a row from the height on reads 0. A program of the first format is one group: an `at` of a main column that
  * any step assigns is refused. The same refusals as there.
  *   inputs: an ms_dev_matrix as for msbb_witness_create_device - elem_bytes 1, 2 or 4 - of width n_inputs and a height in
  * [0, n]; rows at or beyond its height read 0. A 4-byte element >= p is refused, naming the first offender in row-major order
@@ -195,21 +195,66 @@ int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target
  * msbb_witness_create_device (8-byte elements among them); an input height above n; n_inputs > 0 with inputs = NULL; a
  * non-canonical input element; a null w, program or summary. An allocation failure is MS_ERR as well and comes before the
  * first write too: the witness is as it was before the call, and the same call may be made again.
- *   Host waits: one when the program reads inputs of height > 0 (the offender word, before the first write); none otherwise. */
+ *   Host waits: one when the program reads inputs of height > 0 (the offender word, before the first write); none otherwise.
+ *
+ *   SCAN STEPS: columns that follow the previous row (running sums and products, counters, Horner accumulators) - the paragraph
+ * of include/mstark.h read over p = 2^31 - 2^27 + 1. A step is ORDINARY, (dst, root) as above, or a SCAN (dst, mul root A, add
+ * root B, init). The definition is column at a time: step k computes its whole column before step k + 1 starts - for ordinary
+ * steps that equals the definition above. A scan step writes
+ *     trace[0][dst]     = init
+ *     trace[r + 1][dst] = A(r) * trace[r][dst] + B(r)  (mod p),  r = 0 .. n - 2
+ * where A(r), B(r) are the values the roots would have at row r if an ordinary step stood at that position. A(n - 1) and
+ * B(n - 1) are not used: there is no wrap-around, as under is_transition; at n = 1 only init is written. Every written value
+ * is canonical - every stored cell is the Montgomery word of a canonical value. The affine maps x -> A x + B compose
+ * associatively and exactly, so the device's parallel scan is bit-identical to this loop.
+ *   Groups. Each scan step is a group of its own; each maximal run of ordinary steps between scans is a group. Inside a group
+ * the rules above hold (an offset-0 read of an assigned column sees the latest earlier step of the group, shared subexpressions
+ * are computed once, each cell is stored once per group); a read of a column that an earlier group assigned comes from the
+ * trace. A read of main column m at offset 1 by a step of group g is allowed exactly when no step of group g or of any later
+ * group assigns m - with one group this is the rule above - so a later step may read the next row of a finished scan column
+ * (diff = s_next - s; at row n - 1 that is row 0). The `at` rule applies by groups in the same way: an `at` of main column m is
+ * refused when a step of the same or of a later group assigns m, so a later group may read a finished scan column at offset 0,
+ * at offset 1 or at a computed row. The coefficients of a scan step may not read their own dst at either offset, nor index it.
+ *   Blob. A program without a scan step keeps "\0MFILB01" byte for byte. With scans: the magic word 0x3230424C49464D00
+ * ("\0MFILB02") and the layout of "\0MFILL02" - main_width, pre_width, n_inputs, n_nodes, n_steps, n_scans (seven header words
+ * with the magic); the nodes; the steps as [dst, root], root of a scan step being its add root B; n_scans records [step index,
+ * mul root, init] with strictly ascending step indices and init < p. Nodes that no step reaches are not subject to the
+ * offset-1 rule in this format. Each call goes on refusing BOTH magics of the other field as a wrong magic.
+ *   Not part of this: accumulators over the degree-4 extension (four coupled columns that follow the previous row together,
+ * as the running sum of a lookup argument over the challenge field) - a scan step is one base-field column.
+ *   Execution: the groups in order on the context's stream - an ordinary group as above, a scan group as a coefficient pass
+ * (the same kernel, writing A and B as Montgomery words into a column-major temporary) and a three-launch scan over tiles of T
+ * rows (msbb_fill_scan_info tells T): a reduction per tile, ONE workgroup that turns the tile aggregates into the value in
+ * front of each tile, R = 256 aggregates per round with a carry between rounds, and the apply launch that stores each dst cell
+ * once; a circuit of at most T rows takes the apply launch alone. A mul root that is the constant 1 takes the additive form (B
+ * alone, no multiplications). Temporaries of the call: 8 bytes x n (4 when every scan is additive), shared by its scans, plus
+ * 12 bytes per tile, next to the program tables, the scratch of the global-scratch form and the ingest temporary; all of them
+ * are allocated before the first write to the trace, so after an allocation failure the witness is as it was and the same call
+ * may be made again - which matters here, since a later group reads what an earlier group wrote. Host waits are unchanged.
+ * summary for such a program: [1] all steps, [2] instructions per row summed over every launch of the fill kernel, coefficient
+ * passes included, [3] the smallest lanes figure over those launches (0 if any of them uses the global scratch).
+ *   MS_ERR in addition, before anything is written: a length that does not match the three counts; a scan record whose step
+ * index is out of range or not above the one before, whose mul root is out of range or whose init is >= p; a scan step whose
+ * coefficients read its own dst; an offset-1 read or an `at` that the group rule refuses. */
 int32_t msbb_witness_fill(msbb_witness* w, size_t circuit, const uint8_t* program, size_t program_len,
                           const ms_dev_matrix* inputs /* nullable with n_inputs 0 */, void* producer_stream /* hipStream_t, nullable */,
                           uint64_t summary[4]);
 /* Host code, no device: checks a fill program as msbb_witness_fill does (everything that needs no witness) and describes how it
  * would run: out4 = [instructions per row, live slots, lanes per workgroup of the LDS form (0: global scratch), distinct assigned
- * columns]. Texts start "msbb_fill_program_info: ". */
+ * columns]. Texts start "msbb_fill_program_info: ". For a program with scan steps: instructions summed over the launches of the
+ * fill kernel, the largest slot count and the smallest lanes figure among them, and the dst columns of scan steps count as
+ * assigned. */
 int32_t msbb_fill_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
+/* Host code, no device: the same checks, and out4 = [scan steps, launches of the fill kernel (one per group of ordinary steps,
+ * one coefficient pass per scan), scans in the additive form, T = rows per scan tile]. Texts start "msbb_fill_scan_info: ". */
+int32_t msbb_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
 
 /* ---- The sorting permutation of a circuit's rows, made on the device: ms_witness_argsort (include/mstark.h, "The sorting
  * permutation of a circuit's rows") for this configuration, its definition read over p = 2^31 - 2^27 + 1: row i comes before
  * row j iff (trace[i][k_0], ..., trace[i][k_{m-1}], i) is lexicographically smaller, 1 <= m <= 8, a column may repeat among the
  * keys, ties go by row index, MS_SORT_PERM / MS_SORT_RANK as there. With msbb_witness_fill's indexed reads behind it a sorted
- * copy of a column - a memory log in address order, a range check by sorted differences - is made without leaving HBM: sort,
- * then gather. What differs from the Goldilocks call:
+ * copy of a column - a memory log in address order, a range check by sorted differences - is made without leaving HBM, and with
+ * its scan steps the running columns over that copy too: sort, gather, scan. What differs from the Goldilocks call:
  *   The system comes from the witness, as for msbb_witness_fill.
  *   Order: cells are compared as the CANONICAL integers in [0, p), not as the Montgomery words that lie in memory (whose order
  * is another one).

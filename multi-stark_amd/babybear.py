@@ -25,7 +25,7 @@ def exported_symbols():
             "msbb_system_preprocessed_mmcs", "msbb_witness_commit_stage1", "msbb_witness_claims_accumulator", "msbb_stage2_build",
             "msbb_pcs_commit_traces", "msbb_quotient", "msbb_pcs_commit_ldes", "msbb_pcs_open", "msbb_witness_check", "msbb_system_check_info",
             "msbb_witness_lookup_balance", "msbb_system_multiplicity_slot", "msbb_witness_derive_multiplicities", "msbb_witness_trace",
-            "msbb_witness_fill", "msbb_fill_program_info", "msbb_witness_argsort", "msbb_sort_info"]
+            "msbb_witness_fill", "msbb_fill_program_info", "msbb_fill_scan_info", "msbb_witness_argsort", "msbb_sort_info"]
 
 
 import sys
@@ -81,6 +81,22 @@ def fill_program_info(program):
     return dict(zip(["instructions", "slots", "lds_lanes", "assigned_columns"], (int(x) for x in o)))
 
 
+def fill_scan_info(program):
+    """msbb_fill_scan_info (host only): checks a fill program and tells its scan steps -> (scan steps, launches of the fill kernel
+    (one per group of ordinary steps, one coefficient pass per scan), scans in the additive form, T = rows per scan tile)"""
+    a, o = _pkg()._program_bytes(program), np.zeros(4, dtype=np.uint64)
+    _check(_lib().msbb_fill_scan_info(a.ctypes.data_as(u8p), C.c_size_t(a.size), o.ctypes.data_as(u64p)))
+    return tuple(int(x) for x in o)
+
+
+def compile_fill(main_width, preprocessed_width, n_inputs, steps):
+    """frontend.compile_fill over this field, scan steps (frontend.scan, running_sum, running_product) included: the program
+    is authored under frontend.field(BABYBEAR) - build the expressions under it too where they hold constants, which are folded
+    modulo the field in force - and a program with scans comes out in the second format, "\\0MFILB02". -> frontend.FillProgram"""
+    with frontend.field(frontend.BABYBEAR):
+        return frontend.compile_fill(main_width, preprocessed_width, n_inputs, steps, scans=True)
+
+
 def sort_info():
     """msbb_sort_info (host only) -> (T = rows per tile, bits per digit, R = per-tile counts per round of the offsets step,
     largest number of key columns) of Witness.argsort"""
@@ -102,7 +118,7 @@ class Witness:
         return _pkg().SortReport(*(int(x) for x in summary))
 
     def fill(self, circuit, program, inputs=None, stream=None):
-        """msbb_witness_fill: the columns of `circuit` that `program` (frontend.compile_fill under field(BABYBEAR), or its blob)
+        """msbb_witness_fill: the columns of `circuit` that `program` (babybear.compile_fill, or its blob; scan steps included)
         assigns, evaluated on the device for every row. inputs: None or a 2-D matrix in device memory (torch tensor or
         __cuda_array_interface__; 1, 2 or 4-byte elements read as unsigned canonical values; any strides) of at most the
         circuit's height, rows beyond it read 0. stream: as for System.witness_from_device. -> the package's FillReport"""

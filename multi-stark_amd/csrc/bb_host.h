@@ -199,6 +199,8 @@ void multiplicity_slot(const BCircuit& c, size_t slot, u64 out3[3]);  // msbb_sy
 void witness_fill(BSystem& sys, BWitness& wit, size_t circuit, const uint8_t* program, size_t program_len, const ms_dev_matrix* inputs,
                   void* producer_stream, u64 summary[4]);
 void fill_program_info(const uint8_t* program, size_t program_len, u64 out4[4]);  // host only: [instructions, slots, LDS lanes, assigned columns]
+// msbb_fill_scan_info: host only - [scan steps, launches of the fill kernel, scans in the additive form, rows per scan tile]
+void fill_scan_info(const uint8_t* program, size_t program_len, u64 out4[4]);
 // msbb_witness_argsort (bb_argsort.hip): the stable sorting permutation of circuit `ci`'s rows under the key columns, cells compared
 // as canonical values (or its inverse, what = 1), written into main column dst as Montgomery words. One host wait: the digit histograms
 void witness_argsort(BSystem& sys, BWitness& wit, size_t ci, const uint32_t* key_columns, size_t n_keys, uint32_t dst, uint32_t what,

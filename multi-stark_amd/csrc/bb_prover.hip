@@ -1584,6 +1584,13 @@ int32_t msbb_fill_program_info(const uint8_t* program, size_t program_len, uint6
   return MS_OK;
   BB_CATCH
 }
+int32_t msbb_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t out4[4]) {
+  BB_TRY
+  if (!program || !out4) throw std::runtime_error("msbb_fill_scan_info: null argument");
+  fill_scan_info(program, program_len, out4);
+  return MS_OK;
+  BB_CATCH
+}
 int32_t msbb_witness_argsort(msbb_witness* w, size_t circuit, const uint32_t* key_columns, size_t n_keys, uint32_t dst_column, uint32_t what,
                              uint64_t summary[4]) {
   BB_TRY

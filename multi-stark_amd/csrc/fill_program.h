@@ -11,7 +11,7 @@
 // instruction order; what no final assignment needs is dropped, and slots are allocated by liveness as build_program does for
 // DProgram. The final instance of every assigned column stays live to the end, where each assigned cell is stored once.
 //
-// A program with SCAN steps (the second format, magic "\0MFILL02") is cut into GROUPS: every scan step is one, every maximal run
+// A program with SCAN steps (the second format, magic "\0MFILL02" / "\0MFILB02") is cut into GROUPS: every scan step is one, every maximal run
 // of ordinary steps between scans is one. The part above (fill_linearise) runs once per ordinary group and, for a scan, once as a
 // COEFFICIENT PASS over its two roots (mul, add), or over the add root alone when the mul root is the constant 1: a pseudo-group
 // whose outputs 0 / 1 go to a temporary instead of the trace and bind no column. A read of a column that an earlier group
@@ -43,7 +43,7 @@ struct FillField {
   uint64_t scan_magic;  // the first word of a program with scan steps; 0: this configuration has none
 };
 constexpr FillField FILL_GOLDILOCKS{0x31304C4C49464D00ull, 0xFFFFFFFF00000001ull, 64, 0x32304C4C49464D00ull};  // "\0MFILL01", "\0MFILL02"
-constexpr FillField FILL_BABYBEAR{0x3130424C49464D00ull, 0x78000001ull, 32, 0};                                // "\0MFILB01"
+constexpr FillField FILL_BABYBEAR{0x3130424C49464D00ull, 0x78000001ull, 32, 0x3230424C49464D00ull};            // "\0MFILB01", "\0MFILB02"
 
 constexpr uint32_t FL_NONE = ~0u;
 constexpr uint32_t FL_SRC_PRE = 0, FL_SRC_MAIN = 1, FL_SRC_INPUT = 3;

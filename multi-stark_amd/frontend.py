@@ -31,12 +31,14 @@ N_AT = 22  # an indexed read: column a of `source` at the row that node b comput
 SRC_INPUT = 3
 FILL_MAGIC = 0x31304C4C49464D00  # "\0MFILL01"; over BabyBear "\0MFILB01": a fill program belongs to the field its constants were folded in
 FILL_BITS = 64  # bits(x, lo, length) needs lo + length <= the width of a value: 64, over BabyBear 32
+FILL_SCAN_MAGIC = 0x32304C4C49464D00  # "\0MFILL02": a program with scan steps; over BabyBear "\0MFILB02"
 
 # The two StarkGenericConfig instantiations of the reference: GoldilocksBlake3Config (src/types.rs:24-29,199-223) and
 # the BabyBear / degree-4 extension / Poseidon2 test configuration (src/test_circuits/baby_bear_config.rs:28-38).
-GOLDILOCKS = dict(name="goldilocks", P=P, EXT_D=2, EXT_W=7, BLOB_MAGIC=0x31305359534D0000, FILL_MAGIC=0x31304C4C49464D00, FILL_BITS=64)
+GOLDILOCKS = dict(name="goldilocks", P=P, EXT_D=2, EXT_W=7, BLOB_MAGIC=0x31305359534D0000, FILL_MAGIC=0x31304C4C49464D00, FILL_BITS=64,
+                  FILL_SCAN_MAGIC=0x32304C4C49464D00)
 BABYBEAR = dict(name="babybear", P=(1 << 31) - (1 << 27) + 1, EXT_D=4, EXT_W=11, BLOB_MAGIC=0x31304259534D0000, FILL_MAGIC=0x3130424C49464D00,
-                FILL_BITS=32)
+                FILL_BITS=32, FILL_SCAN_MAGIC=0x3230424C49464D00)
 
 
 @contextlib.contextmanager
@@ -44,7 +46,7 @@ def field(cfg):
     """Author circuits / witnesses / blobs over another configuration's field: `with frontend.field(frontend.BABYBEAR):`.
     (The reference picks the field through the SC type parameter; this front-end keeps it in module state.)"""
     g = globals()
-    saved = {k: g[k] for k in ("P", "EXT_D", "EXT_W", "BLOB_MAGIC", "FILL_MAGIC", "FILL_BITS")}
+    saved = {k: g[k] for k in ("P", "EXT_D", "EXT_W", "BLOB_MAGIC", "FILL_MAGIC", "FILL_BITS", "FILL_SCAN_MAGIC")}
     g.update({k: cfg[k] for k in saved})
     try:
         yield cfg
@@ -685,9 +687,6 @@ class _FillInterner(_Interner):
         return {N_ADD: self.add, N_SUB: self.sub, N_MUL: self.mul, N_LT: self.lt, N_XOR: self.xor, N_AND: self.and_}[k](a, b)
 
 
-FILL_SCAN_MAGIC = 0x32304C4C49464D00  # "\0MFILL02": a program with scan steps (Goldilocks configuration only)
-
-
 class Scan:
     """The right-hand side of a scan step (scan, running_sum, running_product): dst[0] = init, dst[r + 1] = mul(r) * dst[r] + add(r)"""
 
@@ -762,20 +761,22 @@ def _main_reads(nodes):
     return reads
 
 
-def compile_fill(main_width, preprocessed_width, n_inputs, steps):
+def compile_fill(main_width, preprocessed_width, n_inputs, steps, scans=None):
     """steps: [(dst_column, Expr or scan(...))], run in order, each for every row (include/mstark.h, ms_witness_fill).
     Every scan step is a group of its own and every run of ordinary steps between scans is one; the next row of a main column
-    may be read only where no step of the same or a later group assigns it. -> FillProgram"""
+    may be read only where no step of the same or a later group assigns it. scans: None - scan steps are accepted under the
+    Goldilocks field alone; True - under either field (babybear.compile_fill passes it). -> FillProgram"""
     spec = {"main_width": int(main_width), "preprocessed_width": int(preprocessed_width), "n_inputs": int(n_inputs)}
     it = _FillInterner()
-    out, scans = [], []
+    any_field, out, scans = bool(scans), [], []
     for k, (dst, e) in enumerate(steps):
         dst = int(dst)
         if not 0 <= dst < spec["main_width"]:
             raise CompileError("DstOutOfRange step=%d dst=%d main_width=%d" % (k, dst, spec["main_width"]))
         if isinstance(e, Scan):
-            if FILL_MAGIC != GOLDILOCKS["FILL_MAGIC"]:
-                raise CompileError("ScanStepInThisField step=%d: scan steps: Goldilocks configuration only" % k)
+            if FILL_MAGIC != GOLDILOCKS["FILL_MAGIC"] and not any_field:
+                raise CompileError("ScanStepInThisField step=%d: scan steps: Goldilocks configuration only "
+                                   "(unless compile_fill(..., scans=True), as babybear.compile_fill passes)" % k)
             if not 0 <= e.init < P:
                 raise CompileError("ScanInitOutOfRange step=%d init=%d: the first value of a scan column is an integer in [0, P)" % (k, e.init))
             scans.append((k, it.compile_fill_expr(e.mul, spec), e.init))

@@ -23,6 +23,12 @@ msbb_witness_fill alone) against the host route, frontend._u32_add_traces (numpy
 the same program without them (the difference is what the scans cost), the running sum alone in the additive form (multiplier
 the constant 1) and in the affine form (multiplier an input column of ones), and the host route the scans replace -
 ms_witness_trace, one sequential loop over the rows, ms_witness_create.
+  python tools/witness_fill.py --scan --config babybear [--log-size 20] [--reps 9]
+the same leg over BabyBear (msbb_witness_fill): the halves program plus a base-field Horner accumulator and a running sum of the
+carries, with and without the scans, the running sum alone in both forms (no inputs: the multiplier of the affine form is the
+activity column, all ones), and the host route - msbb_witness_trace, numpy and one sequential loop, msbb_witness_create. The
+bytes each scan moves by its layout (28 per row in the affine form, 16 in the additive, plus what its coefficient pass reads)
+over the measured time is printed next to them; it is no share of a peak.
   python tools/witness_fill.py --gather [--config babybear] [--log-size 20] [--reps 9]
 --gather: the price of an indexed read (frontend.Expr.main_at). A test circuit of 4 columns - a value, the identity index, a
 random permutation, and the column that is written - is filled by three one-step programs in turn: the value through the
@@ -50,7 +56,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="goldilocks", choices=["goldilocks", "babybear"])
 ap.add_argument("--log-size", type=int, default=20)
 ap.add_argument("--reps", type=int, default=9)
-ap.add_argument("--scan", action="store_true", help="the scan-step leg (Goldilocks)")
+ap.add_argument("--scan", action="store_true", help="the scan-step leg (both configurations)")
 ap.add_argument("--gather", action="store_true", help="the indexed-read leg (both configurations)")
 ap.add_argument("--alone", action="store_true", help="ms_witness_fill of U32Add alone in the process (Goldilocks)")
 args = ap.parse_args()
@@ -223,6 +229,115 @@ def scan_leg():
     state.clear()  # witnesses go before their system
 
 
+def scan_leg_bb():
+    """--scan --config babybear: what scan steps cost over BabyBear. One circuit of 16 columns: the 14 of U32Add from the 16-bit
+    halves, a Horner accumulator over the sum words (column 14) and a running sum of the carries (column 15)."""
+    bb = pkg.babybear
+    k = fe.poseidon2_constants()
+    bb.set_poseidon2(ctx, k)
+    E = fe.Expr
+    p = fe.BABYBEAR["P"]
+    alpha = (1 << 27) + 3
+    with fe.field(fe.BABYBEAR):
+        plain = list(zip([d for d, _ in fe.u32_add_halves_fill_program(n).steps], halves_roots(n)))
+        z = E.main(8) + E.main(9) * 256 + E.main(10) * 65536 + E.main(11) * (1 << 24)
+        scans = [(14, fe.scan(alpha, z)), (15, fe.running_sum(E.main(12)))]
+        prog_scans, prog_plain = bb.compile_fill(16, 0, 4, plain + scans), bb.compile_fill(16, 0, 4, plain)
+        sum_additive = bb.compile_fill(16, 0, 0, [(15, fe.running_sum(E.main(12)))])
+        sum_affine = bb.compile_fill(16, 0, 0, [(15, fe.scan(E.main(13), E.main(12)))])  # the multiplier as a column of ones: the affine form
+        system = bb.System.new(ctx, fe.test_params(), [fe.CircuitInputs(16, None, [E.main(12) * E.main(12) - E.main(12)], [], [])], k)
+        packed = fe.pack_claims([])
+    for name, pr in (("with the two scans", prog_scans), ("without them", prog_plain), ("running sum, additive", sum_additive),
+                     ("running sum, affine", sum_affine)):
+        print("program %-24s %d steps; %s; scan info %s" % (name + ":", len(pr.steps), bb.fill_program_info(pr), bb.fill_scan_info(pr)))
+    xs, ys = fe.xorshift_pairs(n)
+    m16, s16 = np.uint64(0xFFFF), np.uint64(16)
+    inputs = torch.from_numpy(np.stack([xs & m16, xs >> s16, ys & m16, ys >> s16], axis=1).astype(np.uint16).view(np.int16)).cuda()
+    w = system.witness_from_device([torch.zeros((n, 16), dtype=torch.int32, device="cuda")], packed)
+
+    def host_loop(t):
+        """the two columns as the host makes them: numpy for the sum words and the running sum, one sequential loop for Horner"""
+        t = t.astype(np.uint64)
+        zs = ((t[:, 8] + t[:, 9] * 256 + t[:, 10] * 65536 + t[:, 11] * (1 << 24)) % p).tolist()
+        acc, h = 0, [0] * n
+        for i in range(n):
+            h[i] = acc
+            acc = (alpha * acc + zs[i]) % p
+        t[:, 14] = np.array(h, dtype=np.uint64)
+        t[1:, 15] = np.cumsum(t[:-1, 12]) % p
+        t[0, 15] = 0
+        return t
+
+    rep = w.fill(0, prog_scans, inputs)
+    print("2^%d rows, filled with the scans: %s" % (args.log_size, rep))
+    with fe.field(fe.BABYBEAR):
+        want = np.zeros((n, 16), dtype=np.uint64)
+        want[:, :14] = fe._u32_add_traces(xs, ys, n)[0][1]
+    want = host_loop(want)
+    same = bool(np.array_equal(w.trace(0).astype(np.uint64), want))
+    w.fill(0, sum_affine)
+    same_affine = bool(np.array_equal(w.trace(0).astype(np.uint64), want))
+    print("trace equals the host's: %s; the running sum again in the affine form: %s" % (same, same_affine), flush=True)
+    assert same and same_affine
+
+    print("\n# babybear, 2^%d rows: the routes, alternating" % args.log_size)
+    state = {}
+
+    def fill(prog, inp):
+        def run():
+            w.fill(0, prog, inp)
+            ctx.sync()
+        return run
+
+    def host_read():
+        state["t"] = w.trace(0)
+
+    def host_scan():
+        state["t"] = host_loop(state["t"])
+
+    def host_create():
+        state["host"] = None  # (the previous upload's memory goes back first)
+        state["host"] = system.witness([state["t"]], packed)
+
+    t_sc, t_pl, t_add, t_aff, t_rd, t_lp, t_cr = timed([fill(prog_scans, inputs), fill(prog_plain, inputs), fill(sum_additive, None), fill(sum_affine, None),
+                                                        host_read, host_scan, host_create], args.reps)
+    line("msbb_witness_fill with the two scans", t_sc)
+    line("msbb_witness_fill without them", t_pl)
+    line("running sum alone, additive form (no inputs)", t_add)
+    line("running sum alone, affine form (multiplier column)", t_aff)
+    line("host: msbb_witness_trace", t_rd)
+    line("host: numpy and the sequential loop (Python integers)", t_lp)
+    line("host: msbb_witness_create", t_cr)
+    total = [a + b + c for a, b, c in zip(t_rd, t_lp, t_cr)]
+    moved = [a + c for a, c in zip(t_rd, t_cr)]
+    line("host route, the three steps together", total)
+    line("host route without its loop (read back + create)", moved)
+    m = statistics.median
+    cost = m(t_sc) - m(t_pl)
+    print("the two scans cost %.3f ms; host route / fill = %.0f, without the loop %.1f; affine / additive = %.2f" % (
+        cost, m(total) / m(t_sc), m(moved) / m(t_sc), m(t_aff) / m(t_add)))
+    # bytes by the layout: affine 28 per row and additive 16; the Horner pass reads 4 columns (16), the sum's pass 1 (4)
+    both, add_b, aff_b = (28 + 16 + 16 + 4) * n, (16 + 4) * n, (28 + 8) * n
+    print("bytes by the layout / time: the two scans %d B/row in %.3f ms = %.0f GB/s; additive alone %d B/row, whole call %.3f ms = %.0f GB/s; "
+          "affine alone %d B/row, whole call %.3f ms = %.0f GB/s" % (
+              both // n, cost, both / cost / 1e6 if cost > 0 else float("nan"), add_b // n, m(t_add), add_b / m(t_add) / 1e6,
+              aff_b // n, m(t_aff), aff_b / m(t_aff) / 1e6))
+    assert np.array_equal(w.trace(0).astype(np.uint64), want)
+    state.clear()  # witnesses go before their system
+
+
+def halves_roots(num_adds):
+    """the right-hand sides of frontend.u32_add_halves_fill_program, in its order of steps (call under field(BABYBEAR))"""
+    E = fe.Expr
+    x_lo, x_hi, y_lo, y_hi = (E.input(k) for k in range(4))
+    s_lo = x_lo + y_lo
+    s_hi = x_hi + y_hi + fe.bits(s_lo, 16, 1)
+    roots = []
+    for lo, hi in ((x_lo, x_hi), (y_lo, y_hi), (s_lo, s_hi)):
+        roots += [fe.bits(lo, 0, 8), fe.bits(lo, 8, 8), fe.bits(hi, 0, 8), fe.bits(hi, 8, 8)]
+    return roots + [fe.bits(s_hi, 16, 1), fe.lt(E.row(), num_adds)]
+
+
 def gather_leg():
     """--gather: what an indexed read costs. One circuit of 4 columns (value, identity index, a random permutation, out); three
     one-step programs write `out` and alternate: the value through the identity index, through the permutation, and as the
@@ -295,6 +410,9 @@ if args.gather:
     sys.exit(0)
 if args.alone:
     alone_leg()
+    sys.exit(0)
+if args.scan and args.config == "babybear":
+    scan_leg_bb()
     sys.exit(0)
 if args.config == "babybear":
     babybear()
