@@ -1,53 +1,21 @@
-// Trace columns filled on the device from a program (ms_witness_fill; the definition is in include/mstark.h): the caller
-// authors, in the front end, how each dependent column of one circuit follows from inputs and other columns - an ordered list
-// of steps (dst column, expression) over the constraint algebra plus the witness-only nodes row / bits / inv0 / lt / xor / and -
-// and the device evaluates it for every row of the witness's row-major trace.
+// ms_witness_fill (the Goldilocks configuration): what the shared kernels and driver of fill_dev.h need to know of Goldilocks.
 //
-// Host side (fill_compile in fill_program.h, no device needed, shared with the BabyBear configuration): the blob is checked in
-// full, then linearised into hash-consed instances with slots allocated by liveness; here it runs with the Goldilocks parameters
-// (magic, modulus, 64-bit values).
+// What differs in this field: slots are the 8-byte values as they lie in memory, and the scan computes on the same words. The
+// trace, the preprocessed trace, the ingested inputs and the temporary of a coefficient pass are row-major, a cell is
+// buf[row * width + col]: a scan thread loads the (A, B) of a row with one 16-byte load from the n x 2 temporary (n x 1, B
+// alone, in the additive form) and stores each of its four dst cells with a strided 8-byte store, and a tile's aggregate lies
+// interleaved, (a, b) at aggs[2 t]. When the witness holds lookup values for the circuit, lookup_values_k recomputes them
+// behind the last group.
 //
-// Device side: fill_k, one thread per row. The slot file is [slot][lane] - in LDS at 256 / 128 / 64 lanes per workgroup (lane l
-// touches the 8-byte words slot * lanes + l: consecutive lanes, consecutive words, no bank conflict), or, when it does not fit
-// 64 KB at 64 lanes, in a global scratch walked in row batches (tiers 1 and 4 of check_dev.h, by the placement rules of
-// msamd.h). Rows are independent: offset-1 reads of the main trace, and reads of it at a computed row (OP_AT, "INDEXED READS"),
-// are refused for every column the program assigns, so no thread reads what another one writes. An indexed read is one scattered
-// 8-byte load of trace, preprocessed trace or inputs, guarded by the source's height: a row from the height on loads nothing.
-//
-// Order on the context's stream: program upload, [wait for the producer's stream, ingest of the inputs into a row-major
-// temporary with the offender word, ONE host wait for that word], fill_k, lookup_values_k when the witness holds lookup values
-// for the circuit. Every refusal comes before fill_k is launched.
-//
-// SCAN steps (a program of the second format): trace[0][dst] = init, trace[r+1][dst] = A(r) * trace[r][dst] + B(r). The groups
-// of the program run in order on the stream: an ordinary group is one fill_k launch as above; a scan group is its COEFFICIENT
-// PASS - fill_k over the roots A, B with an n x 2 row-major temporary as its output (16 bytes per row; n x 1, B alone, when A is
-// the constant 1: the ADDITIVE form, no multiplications) - and then the scan of the affine maps x -> a x + b, whose composition
-// is associative and exact, so the parallel result equals the sequential loop bit for bit. Row r carries the map (A(r-1), B(r-1)),
-// row 0 the map (1, init), and the value before row 0 is 0. A tile is FL_SCAN_TILE = 256 threads x 4 consecutive rows:
-//   (a) scan_reduce_k   one workgroup per tile composes its rows into one aggregate: a thread composes its 4 rows, a wave scans
-//                       the 64 thread aggregates with shuffles, the 4 wave aggregates are joined through LDS
-//   (b) scan_starts_k   ONE workgroup turns the tile aggregates into the value in front of each tile, 256 aggregates per round
-//                       with the value behind the round carried into the next
-//   (c) scan_apply_k    one workgroup per tile scans its rows again from that value and stores the dst cells, each once
-// and a circuit of at most one tile takes launch (c) alone. No workgroup waits for another inside a kernel: the three phases are
-// ordered by the launches. Bytes per row and scan: 16 written by the coefficient pass, 16 read by (a), 16 read and 8 written by
-// (c) - 56 (additive: 8 + 8 + 8 + 8 = 32), next to what the pass itself reads; (a) and (b) move 24 / 1024 bytes per row more.
-// Temporaries of the call: 16 bytes x n (8 when every scan is additive), shared by its scans, and 24 bytes per tile.
-//
-// PEER READS (the third format): source 4 + k of OP_VAR / OP_AT reads entry k of FlParams::peer, the main or preprocessed trace
-// of ANOTHER circuit of the witness, with that matrix's own height as the bound. The driver resolves the program's records
-// against the system and the witness and refuses before any launch; the call writes no peer, so nothing else changes.
-#include <algorithm>
-
-#include "fill_program.h"
+// PEER READS (the third format) exist in this field alone: source 4 + k of OP_VAR / OP_AT reads entry k of View::peers, the
+// main or preprocessed trace of ANOTHER circuit of the witness, with that matrix's own height as the bound. resolve_peers
+// checks the program's records against the system and the witness and refuses before any launch; the call writes no peer.
+#include "fill_dev.h"
 #include "host.h"
-#include "ingest.h"
 
 namespace msamd {
 
 namespace {
-
-constexpr const char* FL_CALL = "ms_witness_fill";
 
 struct FlPeer {  // a peer read's matrix: another circuit's main or preprocessed trace, h x w row-major (h = 0: inactive, p unused)
   const u64* p;
@@ -55,222 +23,142 @@ struct FlPeer {  // a peer read's matrix: another circuit's main or preprocessed
   uint32_t w;
 };
 
-struct FlParams {
-  const u64* trace;           // n x main_w row-major, read
-  u64* out;                   // n x out_w row-major, written: the trace (out_w = main_w), or the temporary of a coefficient pass
-  uint32_t out_w;
-  const u64 *pre, *inp;       // n x pre_w and h_in x n_in, row-major
-  size_t n, h_in;
-  uint32_t main_w, pre_w, n_in;
-  const uint32_t* code;
-  const u64* consts;
-  const uint32_t* outs;
-  uint32_t n_instr, n_outs;
-  size_t row0, rows;
-  u64* scratch;
-  FlPeer peer[FL_MAX_PEERS];  // source 4 + k; indexed by the instruction word alone, so the lookup is wave-uniform
-};
+struct GlFill {
+  using Word = u64;
+  static constexpr u32 BITS = 64;
+  static constexpr u64 P = GL_P;
+  static constexpr bool PEERS = true;
+  static constexpr const char* call = "ms_witness_fill";
+  static constexpr FillField magic = FILL_GOLDILOCKS;
+  static __device__ __forceinline__ u64 add(u64 a, u64 b) { return gl_add(a, b); }
+  static __device__ __forceinline__ u64 sub(u64 a, u64 b) { return gl_sub(a, b); }
+  static __device__ __forceinline__ u64 mul(u64 a, u64 b) { return gl_mul(a, b); }
+  static __device__ __forceinline__ u64 neg(u64 a) { return gl_neg(a); }
+  static __device__ __forceinline__ u64 inv0(u64 a) { return gl_inv(a); }  // (the chain x^(p - 2) maps 0 to 0)
+  static __device__ __forceinline__ u64 load(u64 w) { return w; }
+  static __device__ __forceinline__ u64 stored(u64 v) { return v; }
+  static __device__ __forceinline__ u64 row(size_t r) { return (u64)r; }
 
-template <bool LDS>
-__global__ __launch_bounds__(256) void fill_k(FlParams p) {
-  extern __shared__ __attribute__((aligned(16))) u64 sm[];
-  const u32 tid = threadIdx.x;
-  const size_t t = blockIdx.x * size_t(blockDim.x) + tid;
-  if (t >= p.rows) return;  // (no barrier below: every lane owns its column of the slot file)
-  const size_t r = p.row0 + t, rn = r + 1 == p.n ? 0 : r + 1;
-  u64* slots = LDS ? (sm + tid) : (p.scratch + t);
-  const size_t stride = LDS ? blockDim.x : p.rows;
-  for (u32 pc = 0; pc < p.n_instr; pc++) {
-    const uint4 ins = reinterpret_cast<const uint4*>(p.code)[pc];
-    u64 v;
-    switch (ins.x) {
-      case OP_CONST: v = p.consts[ins.z]; break;
-      case OP_VAR: {
-        const u32 src = ins.z & 0xff;
-        const size_t row = (ins.z >> 8) ? rn : r;
-        if (src == FL_SRC_MAIN)
-          v = p.trace[row * p.main_w + ins.w];
-        else if (src == FL_SRC_PRE)
-          v = p.pre[row * p.pre_w + ins.w];
-        else if (src == FL_SRC_INPUT)
-          v = row < p.h_in ? p.inp[row * p.n_in + ins.w] : 0;
-        else {  // a peer, by THIS circuit's row: a row from the peer's height on loads nothing
-          const FlPeer& q = p.peer[src - FL_SRC_PEER];
-          v = row < q.h ? q.p[row * q.w + ins.w] : 0;
-        }
-        break;
-      }
-      case OP_AT: {  // [row slot, source | column << 8]: the bound check is the definition, a row from the height on loads nothing
-        const u64 i = slots[ins.z * stride];
-        const u32 src = ins.w & 0xff;
-        const size_t col = ins.w >> 8;
-        v = 0;
-        if (src >= FL_SRC_PEER) {
-          const FlPeer& q = p.peer[src - FL_SRC_PEER];
-          if (i < (u64)q.h) v = q.p[(size_t)i * q.w + col];
-        } else if (i < (u64)(src == FL_SRC_INPUT ? p.h_in : p.n)) {
-          const size_t row = (size_t)i;
-          v = src == FL_SRC_MAIN ? p.trace[row * p.main_w + col] : src == FL_SRC_PRE ? p.pre[row * p.pre_w + col] : p.inp[row * p.n_in + col];
-        }
-        break;
-      }
-      case OP_ROW: v = (u64)r; break;
-      case OP_ADD: v = gl_add(slots[ins.z * stride], slots[ins.w * stride]); break;
-      case OP_SUB: v = gl_sub(slots[ins.z * stride], slots[ins.w * stride]); break;
-      case OP_MUL: v = gl_mul(slots[ins.z * stride], slots[ins.w * stride]); break;
-      case OP_NEG: v = gl_neg(slots[ins.z * stride]); break;
-      case OP_BITS: {
-        const u32 length = ins.w >> 8;
-        v = (slots[ins.z * stride] >> (ins.w & 0xff)) & (length == 64 ? ~u64(0) : (u64(1) << length) - 1);  // <= the operand: canonical
-        break;
-      }
-      case OP_INV0: v = gl_inv(slots[ins.z * stride]); break;  // (the chain x^(p - 2) maps 0 to 0)
-      case OP_LT: v = slots[ins.z * stride] < slots[ins.w * stride] ? 1 : 0; break;
-      case OP_XOR: {
-        v = slots[ins.z * stride] ^ slots[ins.w * stride];  // < 2^64 < 2 p
-        if (v >= GL_P) v -= GL_P;
-        break;
-      }
-      default: v = slots[ins.z * stride] & slots[ins.w * stride]; break;  // OP_AND: <= either operand
+  struct Column {  // a scan's dst column: cell r at p[r * w + c]
+    u64* p;
+    uint32_t w, c;
+  };
+  struct View {
+    const u64* d_main;        // n x main_w row-major, read
+    u64* d_out;               // n x out_w row-major, written: the trace (out_w = main_w), or the temporary of a coefficient pass
+    uint32_t out_w;
+    const u64 *d_pre, *d_inp;  // n x pre_w and h_in x n_in, row-major
+    size_t n, h_in;
+    uint32_t main_w, pre_w, n_in;
+    FlPeer peers[FL_MAX_PEERS];  // source 4 + k; indexed by the instruction word alone, so the lookup is wave-uniform
+    __device__ __forceinline__ const u64& main(size_t row, u32 col) const { return d_main[row * main_w + col]; }
+    __device__ __forceinline__ const u64& pre(size_t row, u32 col) const { return d_pre[row * pre_w + col]; }
+    __device__ __forceinline__ const u64& inp(size_t row, u32 col) const { return d_inp[row * n_in + col]; }
+    __device__ __forceinline__ u64 peer(u32 k, u64 row, u32 col) const {  // a row from the peer's height on loads nothing
+      const FlPeer& q = peers[k];
+      return row < (u64)q.h ? q.p[(size_t)row * q.w + col] : 0;
     }
-    slots[ins.y * stride] = v;
-  }
-  for (u32 o = 0; o < p.n_outs; o++) p.out[r * p.out_w + p.outs[2 * o]] = slots[p.outs[2 * o + 1] * stride];
-}
+    __device__ __forceinline__ void store(size_t row, u32 col, u64 v) const { d_out[row * out_w + col] = v; }
+    void to_tmp(u64* tmp, uint32_t cols) { d_out = tmp, out_w = cols; }
+    void inputs(const u64* p, size_t h, size_t w) { d_inp = p, h_in = h, n_in = (uint32_t)w; }
+    Column column(uint32_t dst) const { return Column{d_out, main_w, dst}; }
+  };
 
-// ---- scan steps: the affine map x -> a x + b (ADD: a = 1 throughout and is not carried)
-constexpr u32 SC_THREADS = 256, SC_ROWS = 4, SC_TILE = SC_THREADS * SC_ROWS, SC_WAVES = SC_THREADS / 64;
-
-struct Aff {
-  u64 a, b;
-};
-
-struct ScParams {
-  u64* trace;      // n x main_w row-major; column dst is written
-  const u64* tmp;  // the coefficient pass's output: n x 2 (A, B), ADD: n x 1 (B)
-  u64* aggs;       // per tile: (a, b), ADD: b
-  u64* starts;     // per tile: the value in front of its first row (nullptr: one tile, 0)
-  size_t n;
-  u64 init;
-  uint32_t main_w, dst, n_tiles;
-};
-
-template <bool ADD>
-__device__ __forceinline__ Aff sc_then(Aff f, Aff g) {  // f first, then g
-  if (ADD) return Aff{1, gl_add(f.b, g.b)};
-  return Aff{gl_mul(g.a, f.a), gl_add(gl_mul(g.a, f.b), g.b)};
-}
-template <bool ADD>
-__device__ __forceinline__ u64 sc_at(Aff f, u64 x) {
-  return ADD ? gl_add(x, f.b) : gl_add(gl_mul(f.a, x), f.b);
-}
-__device__ __forceinline__ u64 sc_up(u64 v, u32 d) { return (u64)__shfl_up((unsigned long long)v, d, 64); }
-
-// the map of row r: (1, init) at row 0, (A(r-1), B(r-1)) behind it, the identity from row n on
-template <bool ADD>
-__device__ __forceinline__ Aff sc_row(const ScParams& p, size_t r) {
-  if (r >= p.n) return Aff{1, 0};
-  if (r == 0) return Aff{1, p.init};
-  if (ADD) return Aff{1, p.tmp[r - 1]};
-  const ulonglong2 v = reinterpret_cast<const ulonglong2*>(p.tmp)[r - 1];
-  return Aff{v.x, v.y};
-}
-
-// Every thread of the workgroup brings the map of its rows (threads in row order): excl = the maps of all earlier threads
-// composed, total = those of the whole workgroup. sm: SC_WAVES entries; free again on return.
-template <bool ADD>
-__device__ __forceinline__ void sc_block_scan(Aff mine, Aff& excl, Aff& total, Aff* sm) {
-  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  Aff inc = mine;
-  for (u32 d = 1; d < 64; d <<= 1) {
-    Aff prev{ADD ? 1 : sc_up(inc.a, d), sc_up(inc.b, d)};  // (every lane takes part in the shuffle)
-    if (lane >= d) inc = sc_then<ADD>(prev, inc);
-  }
-  if (lane == 63) sm[wave] = inc;
-  Aff pre{ADD ? 1 : sc_up(inc.a, 1), sc_up(inc.b, 1)};
-  if (lane == 0) pre = Aff{1, 0};
-  __syncthreads();
-  Aff before{1, 0};
-  total = Aff{1, 0};
-  for (u32 k = 0; k < SC_WAVES; k++) {
-    const Aff w = sm[k];
-    if (k < wave) before = sc_then<ADD>(before, w);
-    total = sc_then<ADD>(total, w);
-  }
-  excl = sc_then<ADD>(before, pre);
-  __syncthreads();
-}
-
-template <bool ADD>
-__global__ __launch_bounds__(SC_THREADS) void scan_reduce_k(ScParams p) {
-  __shared__ Aff sm[SC_WAVES];
-  const size_t r0 = blockIdx.x * size_t(SC_TILE) + threadIdx.x * SC_ROWS;
-  Aff mine = sc_row<ADD>(p, r0);
-  for (u32 j = 1; j < SC_ROWS; j++) mine = sc_then<ADD>(mine, sc_row<ADD>(p, r0 + j));
-  Aff excl, total;
-  sc_block_scan<ADD>(mine, excl, total, sm);
-  if (threadIdx.x == 0) {
-    if (ADD) {
-      p.aggs[blockIdx.x] = total.b;
-    } else {
-      p.aggs[2 * size_t(blockIdx.x)] = total.a;
-      p.aggs[2 * size_t(blockIdx.x) + 1] = total.b;
+  // ---- the scan: the words as they lie
+  static __device__ __forceinline__ u64 one() { return 1; }
+  static __device__ __forceinline__ u64 sc_mul(u64 a, u64 b) { return gl_mul(a, b); }
+  template <bool ADD>
+  static __device__ __forceinline__ void rows(const ScParams<GlFill>& p, size_t r0, Aff<GlFill> row[SC_ROWS]) {
+    for (u32 j = 0; j < SC_ROWS; j++) {
+      const size_t r = r0 + j;
+      if (r >= p.n) {
+        row[j] = Aff<GlFill>{1, 0};
+      } else if (r == 0) {
+        row[j] = Aff<GlFill>{1, p.init};
+      } else if (ADD) {
+        row[j] = Aff<GlFill>{1, p.tmp[r - 1]};
+      } else {
+        const ulonglong2 v = reinterpret_cast<const ulonglong2*>(p.tmp)[r - 1];
+        row[j] = Aff<GlFill>{v.x, v.y};
+      }
     }
   }
-}
-
-template <bool ADD>
-__global__ __launch_bounds__(SC_THREADS) void scan_starts_k(ScParams p) {  // one workgroup
-  __shared__ Aff sm[SC_WAVES];
-  u64 carry = 0;  // the value in front of the round's first tile
-  for (u32 t0 = 0; t0 < p.n_tiles; t0 += SC_THREADS) {
-    const u32 t = t0 + threadIdx.x;
-    Aff mine{1, 0};
-    if (t < p.n_tiles) mine = ADD ? Aff{1, p.aggs[t]} : Aff{p.aggs[2 * size_t(t)], p.aggs[2 * size_t(t) + 1]};
-    Aff excl, total;
-    sc_block_scan<ADD>(mine, excl, total, sm);
-    if (t < p.n_tiles) p.starts[t] = sc_at<ADD>(excl, carry);
-    carry = sc_at<ADD>(total, carry);
+  static __device__ __forceinline__ void store(const ScParams<GlFill>& p, size_t r0, const u64 cell[SC_ROWS]) {
+    for (u32 j = 0; j < SC_ROWS; j++)
+      if (r0 + j < p.n) p.dst.p[(r0 + j) * p.dst.w + p.dst.c] = cell[j];
   }
-}
-
-template <bool ADD>
-__global__ __launch_bounds__(SC_THREADS) void scan_apply_k(ScParams p) {
-  __shared__ Aff sm[SC_WAVES];
-  const size_t r0 = blockIdx.x * size_t(SC_TILE) + threadIdx.x * SC_ROWS;
-  Aff row[SC_ROWS];
-  for (u32 j = 0; j < SC_ROWS; j++) row[j] = sc_row<ADD>(p, r0 + j);
-  Aff mine = row[0];
-  for (u32 j = 1; j < SC_ROWS; j++) mine = sc_then<ADD>(mine, row[j]);
-  Aff excl, total;
-  sc_block_scan<ADD>(mine, excl, total, sm);
-  u64 x = sc_at<ADD>(excl, p.starts ? p.starts[blockIdx.x] : 0);
-  for (u32 j = 0; j < SC_ROWS; j++) {
-    x = sc_at<ADD>(row[j], x);
-    if (r0 + j < p.n) p.trace[(r0 + j) * p.main_w + p.dst] = x;
+  static __device__ __forceinline__ Aff<GlFill> agg_get(const ScParams<GlFill>& p, u32 t) {
+    return Aff<GlFill>{p.aggs[2 * size_t(t)], p.aggs[2 * size_t(t) + 1]};
   }
-}
-
-template <bool ADD>
-void scan_launch(Ctx& ctx, const ScParams& p) {
-  if (p.n_tiles > 1) {
-    hipLaunchKernelGGL(scan_reduce_k<ADD>, dim3(p.n_tiles), dim3(SC_THREADS), 0, ctx.stream, p);
-    hipLaunchKernelGGL(scan_starts_k<ADD>, dim3(1), dim3(SC_THREADS), 0, ctx.stream, p);
+  static __device__ __forceinline__ void agg_put(const ScParams<GlFill>& p, u32 t, Aff<GlFill> f) {
+    p.aggs[2 * size_t(t)] = f.a;
+    p.aggs[2 * size_t(t) + 1] = f.b;
   }
-  hipLaunchKernelGGL(scan_apply_k<ADD>, dim3(p.n_tiles), dim3(SC_THREADS), 0, ctx.stream, p);
-}
 
-unsigned fl_min_lanes(const FillCode& fc) {
-  unsigned lanes = 256;
-  for (const FillGroup& g : fc.groups) lanes = std::min(lanes, slot_lds_lanes(g.pass.n_slots, 8, 0));
-  return lanes;
-}
+  // ---- the host side
+  static void fail(const std::string& what) { fl_fail<GlFill>(what); }
+  static View accept(HSystem& sys, HWitness& wit, size_t ci) {
+    const size_t C = sys.circuits.size();
+    if (wit.sys != &sys || wit.heights.size() != C) fail("the witness does not belong to this system");
+    if (wit.host_resident) fail("takes a device-resident witness (ms_witness_create, ms_witness_create_device, the generators)");
+    if (wit.has_remote) fail("this witness lacks traces that another rank computes");
+    if (ci >= C) fail("circuit " + std::to_string(ci) + " is out of range");
+    const size_t n = wit.heights[ci];
+    if (!n) fail("circuit " + std::to_string(ci) + " is inactive (height 0)");
+    if (!wit.traces[ci].p) fail("the circuit has no trace on this device");
+    const HCircuit& c = sys.circuits[ci];
+    View v{};
+    v.d_main = v.d_out = wit.traces[ci].p;
+    v.out_w = v.main_w = (uint32_t)c.main_width, v.pre_w = (uint32_t)c.pre_width;
+    v.d_pre = c.pre_width && n == c.pre_height ? c.d_preprocessed.p : nullptr;
+    v.n = n;
+    return v;
+  }
+  static void resolve_peers(HSystem& sys, HWitness& wit, size_t ci, const FillCode& fc, View& v) {  // each record against the system and the witness
+    const size_t C = sys.circuits.size();
+    for (size_t k = 0; k < fc.peers.size(); k++) {
+      const FillPeer& r = fc.peers[k];
+      FlPeer& q = v.peers[k];
+      const std::string at = "peer " + std::to_string(k) + " (circuit " + std::to_string(r.circuit) + ", " + (r.trace ? "main" : "preprocessed") + " trace): ";
+      if (r.circuit >= C) fail(at + "the circuit is out of range (the system has " + std::to_string(C) + ")");
+      if (r.circuit == ci) fail(at + "a peer is another circuit than the one being filled (use source " + std::to_string(r.trace) + " for circuit " + std::to_string(ci) + " itself)");
+      const HCircuit& pc = sys.circuits[r.circuit];
+      const size_t have = r.trace ? pc.main_width : pc.pre_width;
+      if (r.width != have) fail(at + "the program declares width " + std::to_string(r.width) + ", the circuit has " + std::to_string(have));
+      if (r.trace) {
+        q.h = wit.heights[r.circuit];
+        q.p = wit.traces[r.circuit].p;
+        if (q.h && !q.p) fail(at + "the circuit has no trace on this device");
+      } else {
+        q.h = pc.pre_width ? pc.pre_height : 0;
+        q.p = pc.d_preprocessed.p;
+        if (q.h && !q.p) fail(at + "the preprocessed trace is not on the device");
+      }
+      q.w = (uint32_t)r.width;
+    }
+  }
+  static void held_before(HSystem& sys, HWitness& wit, size_t ci) {
+    const HCircuit& c = sys.circuits[ci];
+    if (wit.lookups[ci].mult.p && (!c.prefix_on_device || c.prefix_prog.n_slots * 64 * 8 > 64 * 1024))
+      fail("the witness holds lookup values for circuit " + std::to_string(ci) + " and its lookup prefix does not fit the device sweep");
+  }
+  // SystemWitness::from_stage_1 again for the values the witness holds (checked in held_before: the sweep fits)
+  static void after(HSystem& sys, HWitness& wit, size_t ci) {
+    const HCircuit& c = sys.circuits[ci];
+    DLookups& lk = wit.lookups[ci];
+    if (lk.mult.p && !lookup_values_device(*sys.ctx, c.prefix_prog, wit.traces[ci].p, c.pre_width ? c.d_preprocessed.p : nullptr, wit.heights[ci],
+                                           c.main_width, c.pre_width, c.args_width, lk.mult.p, lk.args.p))
+      fail("internal error (the lookup prefix was found to fit and does not)");
+  }
+  static void ingest(Ctx& ctx, const IngestView& in, u64* out, u64* bad) { ingest_goldilocks(ctx, in, out, bad); }
+  static u64 init(u64 v) { return v; }
+  static bool too_high(size_t n_tiles) { return n_tiles > (size_t(1) << 31); }
+};
 
 }  // namespace
 
 void fill_program_info(const uint8_t* program, size_t program_len, u64 out4[4]) {
-  const FillCode fc = fill_compile(program, program_len, "ms_fill_program_info", FILL_GOLDILOCKS);
-  out4[0] = fc.n_instr, out4[1] = fc.n_slots, out4[2] = fl_min_lanes(fc), out4[3] = fc.n_assigned;
+  fl_program_info<GlFill>(program, program_len, "ms_fill_program_info", out4);
 }
 
 size_t fill_peer_info(const uint8_t* program, size_t program_len, u64* out, size_t cap) {
@@ -280,170 +168,11 @@ size_t fill_peer_info(const uint8_t* program, size_t program_len, u64* out, size
   return fc.peers.size();
 }
 
-void fill_scan_info(const uint8_t* program, size_t program_len, u64 out4[4]) {
-  const FillCode fc = fill_compile(program, program_len, "ms_fill_scan_info", FILL_GOLDILOCKS);
-  size_t launches = 0;
-  for (const FillGroup& g : fc.groups) launches += !g.pass.outs.empty();
-  out4[0] = fc.n_scans, out4[1] = launches, out4[2] = fc.n_additive, out4[3] = SC_TILE;
-}
+void fill_scan_info(const uint8_t* program, size_t program_len, u64 out4[4]) { fl_scan_info<GlFill>(program, program_len, "ms_fill_scan_info", out4); }
 
 void witness_fill(HSystem& sys, HWitness& wit, size_t ci, const uint8_t* program, size_t program_len, const ms_dev_matrix* inputs,
                   void* producer_stream, u64 summary[4]) {
-  Ctx& ctx = *sys.ctx;
-  const std::string name(FL_CALL);
-  auto fail = [&](const std::string& what) -> void { throw std::runtime_error(name + ": " + what); };
-  const size_t C = sys.circuits.size();
-  if (wit.sys != &sys || wit.heights.size() != C) fail("the witness does not belong to this system");
-  if (wit.host_resident) fail("takes a device-resident witness (ms_witness_create, ms_witness_create_device, the generators)");
-  if (wit.has_remote) fail("this witness lacks traces that another rank computes");
-  if (ci >= C) fail("circuit " + std::to_string(ci) + " is out of range");
-  const size_t n = wit.heights[ci];
-  if (!n) fail("circuit " + std::to_string(ci) + " is inactive (height 0)");
-  if (!wit.traces[ci].p) fail("the circuit has no trace on this device");
-  const HCircuit& c = sys.circuits[ci];
-  const FillCode fc = fill_compile(program, program_len, name, FILL_GOLDILOCKS);
-  if (fc.main_w != c.main_width || fc.pre_w != c.pre_width)
-    fail("the program is for main_width " + std::to_string(fc.main_w) + " and preprocessed width " + std::to_string(fc.pre_w) + ", circuit " +
-         std::to_string(ci) + " has " + std::to_string(c.main_width) + " and " + std::to_string(c.pre_width));
-  if (c.pre_width && (n != c.pre_height || !c.d_preprocessed.p)) fail("main trace height must equal preprocessed trace height");
-  // peers: each record against the system and the witness
-  FlPeer peer[FL_MAX_PEERS] = {};
-  for (size_t k = 0; k < fc.peers.size(); k++) {
-    const FillPeer& r = fc.peers[k];
-    const std::string at = "peer " + std::to_string(k) + " (circuit " + std::to_string(r.circuit) + ", " + (r.trace ? "main" : "preprocessed") + " trace): ";
-    if (r.circuit >= C) fail(at + "the circuit is out of range (the system has " + std::to_string(C) + ")");
-    if (r.circuit == ci) fail(at + "a peer is another circuit than the one being filled (use source " + std::to_string(r.trace) + " for circuit " + std::to_string(ci) + " itself)");
-    const HCircuit& pc = sys.circuits[r.circuit];
-    const size_t have = r.trace ? pc.main_width : pc.pre_width;
-    if (r.width != have) fail(at + "the program declares width " + std::to_string(r.width) + ", the circuit has " + std::to_string(have));
-    if (r.trace) {
-      peer[k].h = wit.heights[r.circuit];
-      peer[k].p = wit.traces[r.circuit].p;
-      if (peer[k].h && !peer[k].p) fail(at + "the circuit has no trace on this device");
-    } else {
-      peer[k].h = pc.pre_width ? pc.pre_height : 0;
-      peer[k].p = pc.d_preprocessed.p;
-      if (peer[k].h && !peer[k].p) fail(at + "the preprocessed trace is not on the device");
-    }
-    peer[k].w = (uint32_t)r.width;
-  }
-  DLookups& lk = wit.lookups[ci];
-  const bool held = lk.mult.p != nullptr;
-  if (held && (!c.prefix_on_device || c.prefix_prog.n_slots * 64 * 8 > 64 * 1024))
-    fail("the witness holds lookup values for circuit " + std::to_string(ci) + " and its lookup prefix does not fit the device sweep");
-  IngestView view;
-  size_t h_in = 0;
-  if (fc.n_inputs) {
-    if (!inputs) fail("the program reads " + std::to_string(fc.n_inputs) + " input columns and no input matrix was given");
-    if (inputs->height > n) fail("input height " + std::to_string(inputs->height) + " is above the circuit's height " + std::to_string(n));
-    h_in = (size_t)inputs->height;
-    if (h_in) {
-      try {
-        view = ingest_check(ctx, *inputs, ci, fc.n_inputs, 8);
-      } catch (const std::exception& e) {
-        fail(std::string("input matrix: ") + e.what());
-      }
-    }
-  }
-  summary[0] = n, summary[1] = fc.n_steps, summary[2] = fc.n_instr, summary[3] = fl_min_lanes(fc);
-
-  // the passes of all groups in one code, one constant and one output table; where each pass starts, and its row batch
-  struct Run {
-    const FillGroup* g;
-    size_t code0, consts0, outs0, batch;
-    unsigned lanes;
-  };
-  std::vector<Run> runs;
-  std::vector<uint32_t> code, outs;
-  std::vector<u64> consts;
-  size_t scratch_words = 0;
-  bool any_scan = false, all_additive = true;
-  for (const FillGroup& g : fc.groups) {
-    if (g.pass.outs.empty()) continue;  // no step: nothing to write
-    Run r{&g, code.size(), consts.size(), outs.size(), n, slot_lds_lanes(g.pass.n_slots, 8, 0)};
-    if (!r.lanes) {
-      r.batch = slot_scratch_rows(g.pass.n_slots, 8, n);
-      scratch_words = std::max(scratch_words, r.batch * g.pass.n_slots);
-    }
-    code.insert(code.end(), g.pass.code.begin(), g.pass.code.end());  // (whole instructions: every pass starts 16-byte aligned)
-    consts.insert(consts.end(), g.pass.consts.begin(), g.pass.consts.end());
-    outs.insert(outs.end(), g.pass.outs.begin(), g.pass.outs.end());
-    any_scan |= g.scan;
-    all_additive &= !g.scan || g.additive;
-    runs.push_back(r);
-  }
-  if (runs.empty()) return;
-  const size_t n_tiles = (n + SC_TILE - 1) / SC_TILE;
-  if (any_scan && n_tiles > (size_t(1) << 31)) fail("the circuit is too high for a scan step");
-
-  DBuf<uint32_t> d_code(ctx, code.size()), d_outs(ctx, outs.size());
-  DBuf<u64> d_consts(ctx, std::max<size_t>(consts.size(), 1)), scratch, tmp, aggs, starts;
-  if (scratch_words) scratch = DBuf<u64>(ctx, scratch_words);
-  if (any_scan) {
-    tmp = DBuf<u64>(ctx, n * (all_additive ? 1 : 2));
-    if (n_tiles > 1) aggs = DBuf<u64>(ctx, 2 * n_tiles), starts = DBuf<u64>(ctx, n_tiles);
-  }
-  ctx.h2d(d_code.p, code.data(), code.size() * 4);
-  ctx.h2d(d_outs.p, outs.data(), outs.size() * 4);
-  if (!consts.empty()) ctx.h2d(d_consts.p, consts.data(), consts.size() * 8);
-  ingest_wait_for_producer(ctx, producer_stream);
-  try {
-    DBuf<u64> inp, bad;
-    if (h_in) {
-      inp = DBuf<u64>(ctx, h_in * fc.n_inputs);
-      bad = DBuf<u64>(ctx, 1);
-      HIP_CHECK(hipMemsetAsync(bad.p, 0xFF, 8, ctx.stream));
-      ingest_goldilocks(ctx, view, inp.p, bad.p);
-      u64 bad_h = ~u64(0);
-      ctx.d2h(&bad_h, bad.p, 8);  // the one host wait: nothing has been written yet, and the caller's matrix has been read
-      if (bad_h != ~u64(0))
-        fail("non-canonical input value: row " + std::to_string(bad_h / fc.n_inputs) + ", column " + std::to_string(bad_h % fc.n_inputs));
-    }
-    FlParams p;
-    p.trace = wit.traces[ci].p;
-    p.pre = c.pre_width ? c.d_preprocessed.p : nullptr;
-    p.inp = inp.p;
-    p.n = n, p.h_in = h_in;
-    p.main_w = (uint32_t)c.main_width, p.pre_w = (uint32_t)c.pre_width, p.n_in = (uint32_t)fc.n_inputs;
-    std::copy(peer, peer + FL_MAX_PEERS, p.peer);
-    for (const Run& r : runs) {  // the groups in order; a scan group: its coefficient pass into tmp, then the scan
-      const FillPass& pass = r.g->pass;
-      p.out = r.g->scan ? tmp.p : wit.traces[ci].p;
-      p.out_w = r.g->scan ? (r.g->additive ? 1 : 2) : (uint32_t)c.main_width;
-      p.code = d_code.p + r.code0, p.consts = d_consts.p + r.consts0, p.outs = d_outs.p + r.outs0;
-      p.n_instr = (uint32_t)pass.n_instr, p.n_outs = (uint32_t)(pass.outs.size() / 2);
-      p.row0 = 0, p.rows = n, p.scratch = nullptr;
-      if (r.lanes) {
-        hipLaunchKernelGGL(fill_k<true>, dim3((unsigned)((n + r.lanes - 1) / r.lanes)), dim3(r.lanes), pass.n_slots * r.lanes * 8, ctx.stream, p);
-      } else {
-        p.scratch = scratch.p;
-        for (size_t r0 = 0; r0 < n; r0 += r.batch) {
-          p.row0 = r0;
-          p.rows = std::min(r.batch, n - r0);
-          hipLaunchKernelGGL(fill_k<false>, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, ctx.stream, p);
-        }
-      }
-      HIP_CHECK(hipGetLastError());
-      if (!r.g->scan) continue;
-      ScParams sp;
-      sp.trace = wit.traces[ci].p, sp.tmp = tmp.p, sp.aggs = aggs.p, sp.starts = n_tiles > 1 ? starts.p : nullptr;
-      sp.n = n, sp.init = r.g->init;
-      sp.main_w = (uint32_t)c.main_width, sp.dst = r.g->dst, sp.n_tiles = (uint32_t)n_tiles;
-      if (r.g->additive)
-        scan_launch<true>(ctx, sp);
-      else
-        scan_launch<false>(ctx, sp);
-      HIP_CHECK(hipGetLastError());
-    }
-    // SystemWitness::from_stage_1 again for the values the witness holds (checked above: the sweep fits)
-    if (held && !lookup_values_device(ctx, c.prefix_prog, wit.traces[ci].p, c.pre_width ? c.d_preprocessed.p : nullptr, n, c.main_width, c.pre_width,
-                                      c.args_width, lk.mult.p, lk.args.p))
-      fail("internal error (the lookup prefix was found to fit and does not)");
-  } catch (...) {
-    (void)hipStreamSynchronize(ctx.stream);  // what has been queued may still be reading the caller's matrix
-    abandon_pending();
-    throw;
-  }
+  fl_witness_fill<GlFill>(sys, wit, ci, program, program_len, inputs, producer_stream, summary);
 }
 
 }  // namespace msamd

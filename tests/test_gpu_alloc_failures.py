@@ -101,10 +101,10 @@ def mutate_case(pkg, oracle, ctx, label, s, traces, packed, route, call, want, a
 
 
 # ---------------------------------------------------------------- a. ms_witness_fill
-# The device allocations of witness_fill, csrc/fill.hip: d_code, d_outs (l. 333) and d_consts (l. 334) always; scratch (l. 335)
-# when a group's slot file goes to the global scratch; tmp (l. 337) when there is a scan, and aggs and starts (l. 338) when the
-# height is above one scan tile; inp and bad (l. 347-348) when the program reads inputs. All of them precede the first launch
-# that writes the trace (l. 370), and the held lookup values are recomputed by one launch without an allocation (l. 392).
+# The device allocations of the call, fl_witness_fill in csrc/fill_dev.h (one driver for both fields): d_code, d_outs and d_consts
+# always; scratch when a group's slot file goes to the global scratch; tmp when there is a scan, and aggs and starts when the
+# height is above one scan tile; inp and bad when the program reads inputs. All of them precede the first launch that writes
+# the trace (the group loop), and the held lookup values are recomputed by one launch without an allocation (GlFill::after).
 FILL_ALWAYS, FILL_SCRATCH, FILL_SCAN, FILL_TILES, FILL_INPUTS = 3, 1, 1, 2, 2
 
 
@@ -205,8 +205,9 @@ def test_fill(pkg, fe, actx, oracle, name, route):
     mutate_case(pkg, oracle, actx, "fill %s %s" % (name, route), s, start, packed, route, lambda w: w.fill(ci, prog, d_inputs), want, at_least, after=report)
 
 
-# msbb_witness_fill, csrc/bb_fill.hip: d_code, d_outs (l. 150) and d_consts (l. 151), scratch (l. 155) in the global-scratch form,
-# inp and bad (l. 165-166) with inputs - all before the first launch (l. 183); a witness of this configuration holds no lookup values
+# msbb_witness_fill, the same driver (fl_witness_fill in csrc/fill_dev.h with BbFill of csrc/bb_fill.hip): d_code, d_outs and d_consts,
+# scratch in the global-scratch form, inp and bad with inputs - all before the first launch; a witness of this configuration holds
+# no lookup values
 @pytest.mark.parametrize("name", ["u32_halves", "global_scratch"])
 def test_bb_fill(pkg, actx, name):
     import oracle_bb as ob

@@ -12,10 +12,10 @@ from test_gpu_alloc_failures import actx  # noqa: F401  (a context for sweeps al
 
 pytestmark = pytest.mark.gpu
 
-# The device allocations of witness_fill, csrc/bb_fill.hip: d_code, d_outs (l. 372) and d_consts (l. 373) always; scratch
-# (l. 374) when a group's slot file goes to the global scratch; tmp (l. 376) when there is a scan, and aggs and starts (l. 377)
-# when the height is above one scan tile; inp and bad (l. 387-388) when the program reads inputs. All of them precede the
-# first launch that writes the trace (l. 409 / 415).
+# The device allocations of the call, fl_witness_fill in csrc/fill_dev.h (with BbFill of csrc/bb_fill.hip): d_code, d_outs and
+# d_consts always; scratch when a group's slot file goes to the global scratch; tmp when there is a scan, and aggs and starts
+# when the height is above one scan tile; inp and bad when the program reads inputs. All of them precede the first launch that
+# writes the trace (the group loop).
 FILL_ALWAYS, FILL_SCRATCH, FILL_SCAN, FILL_TILES, FILL_INPUTS = 3, 1, 1, 2, 2
 
 

@@ -12,7 +12,7 @@ from alloc_failure_sweep import own_cache, sweep
 
 pytestmark = pytest.mark.gpu
 
-# The device allocations of witness_fill, csrc/fill.hip: d_code, d_outs and d_consts always; tmp when there is a scan, and aggs
+# The device allocations of the call, fl_witness_fill in csrc/fill_dev.h: d_code, d_outs and d_consts always; tmp when there is a scan, and aggs
 # and starts when the height is above one scan tile; inp and bad when the program reads inputs. Resolving the peers allocates
 # nothing. All of them precede the first launch that writes the trace.
 FILL_ALWAYS, FILL_SCAN, FILL_TILES, FILL_INPUTS = 3, 1, 2, 2

@@ -183,7 +183,7 @@ def chain_program(fe, leaves):
     return fe.compile_fill(6, 2, 3, [(0, t), (3, E.main(0) * E.var(fe.SRC_PRE, 1, 1) + E.main_next(5))])
 
 
-@pytest.mark.parametrize("leaves,form", [(8, (256,)), (40, (64, 128)), (300, (0,))])
+@pytest.mark.parametrize("leaves,form", [(8, (256,)), (40, (64, 128)), (300, (0,)), (70, (64,))])  # (40 slots take 128 lanes, 70 take 64; last: the ids above stay)
 def test_every_kernel_form(pkg, fe, ctx, leaves, form):
     prog = chain_program(fe, leaves)
     info = pkg.fill_program_info(prog)
