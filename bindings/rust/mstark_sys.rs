@@ -211,6 +211,14 @@ extern "C" {
     pub fn ms_fill_scan_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
     /// out: cap x 3 words [circuit, trace, width] per peer; MS_ERR_BUFFER with *n_peers set when cap is too small
     pub fn ms_fill_peer_info(program: *const u8, program_len: usize, out: *mut u64, cap: usize, n_peers: *mut usize) -> i32;
+    /// mode: 0 = MS_CLAIMS_REPLACE, 1 = MS_CLAIMS_APPEND; summary: [rows considered, claims emitted, instructions, LDS lanes]
+    pub fn ms_witness_claims_fill(sys: *mut ms_system, w: *mut ms_witness, circuit: usize, program: *const u8, program_len: usize, rows: usize,
+                                  inputs: *const ms_dev_matrix, producer_stream: *mut c_void, mode: u32, summary: *mut u64) -> i32;
+    /// out4: [instructions, slots, LDS lanes (0: global scratch), W | has_keep << 32]
+    pub fn ms_claims_program_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
+    /// offsets_out: *n_claims + 1 words, data_out: *n_elems; MS_ERR_BUFFER with both counts set when a capacity is too small
+    pub fn ms_witness_claims(w: *mut ms_witness, offsets_out: *mut u64, cap_offsets: usize, data_out: *mut u64, cap_data: usize,
+                             n_claims: *mut usize, n_elems: *mut usize) -> i32;
     /// what: 0 = MS_SORT_PERM, 1 = MS_SORT_RANK; summary: 4 words
     pub fn ms_witness_argsort(sys: *mut ms_system, w: *mut ms_witness, circuit: usize, key_columns: *const u32, n_keys: usize,
                               dst_column: u32, what: u32, summary: *mut u64) -> i32;

@@ -505,6 +505,72 @@ int32_t ms_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t o
 int32_t ms_fill_peer_info(const uint8_t* program, size_t program_len, uint64_t* out /* cap x 3, nullable with cap 0 */, size_t cap,
                           size_t* n_peers);
 
+/* ---- CLAIM PROGRAMS: the claims of a witness built on the device from its traces. Claims can otherwise only be given when a
+ * witness is created, before any column has been filled; for most systems they are a function of filled columns (the bench
+ * workload's [1, x, y, z] per addition). With this call the route pairs -> fill -> claims -> multiplicities -> check -> prove
+ * leaves HBM only for the proof bytes. Goldilocks / BLAKE3 configuration.
+ *   Definition. A claim program has W expressions, the elements of one claim (1 <= W <= 2^16), and optionally a `keep`
+ * expression. They are written in the algebra of fill programs: constants, main / preprocessed / input variables at offset 0
+ * or 1, row, add, sub, mul, neg, bits, inv0, lt, xor, and, and indexed reads (`at`) of the three sources. A claim program
+ * ASSIGNS NOTHING, so neither the offset-1 rule nor the group rule applies: any main column may be read at the next row or at a
+ * computed row. Refused, with a text naming the node: peer sources, publics, selector nodes, stage-2 variables; there are no
+ * scan steps (the format has no record for them, and a fill program handed to this call is refused by its magic).
+ *   ms_witness_claims_fill works on circuit `circuit` of height n, with rows <= n. For each row r in [0, rows), in ascending
+ * order, for which keep(r) != 0 - every row when there is no keep - ONE claim [e_0(r), ..., e_{W-1}(r)] is emitted. Reads mean
+ * what they mean in ms_witness_fill: the next row of row n - 1 is row 0 (n, not `rows`); an input row from the input matrix's
+ * height on reads 0; an index from the source's height on reads 0 and performs no load. Every emitted element is a canonical
+ * field value by construction.
+ *   mode = MS_CLAIMS_REPLACE: the emitted claims become the witness's claims. mode = MS_CLAIMS_APPEND: they follow the claims
+ * the witness already has, whose offsets and elements stay as they are, and the offsets continue. The order of claims is part
+ * of the transcript, so the order of calls is the caller's way to order the claims of several circuits.
+ *   Afterwards the witness is an ordinary device-resident witness: ms_prove, ms_witness_check, ms_witness_lookup_balance,
+ * ms_witness_derive_multiplicities, ms_challenger_observe_claims and ms_witness_claims_accumulator see the new claims. The
+ * traces and the held lookup values are not touched.
+ *   One width per call. A ragged list (claims of several lengths, as a byte-operations chip's are) is made by several calls
+ * with keep masks, one per length and in the order the transcript wants, or on the host as before; one call cannot interleave
+ * lengths.
+ *   summary: [0] rows considered  [1] claims emitted  [2] instructions executed per row  [3] kernel form: lanes per workgroup
+ * with the slot file in LDS, 0 = slots in a global scratch walked in row batches.
+ *   Blob (little-endian 64-bit words), a format of its own: magic 0x314D49414C434D00 ("\0MCLAIM1"), main_width, pre_width,
+ * n_inputs, n_nodes, W, keep root (all ones: none) - seven header words; the nodes, three words each, exactly as in a fill
+ * program; the W element roots, one word each. The length is exactly 7 + 3 n_nodes + W words.
+ *   Execution. The evaluation is the kernel of ms_witness_fill over the first `rows` rows. Without keep it writes straight into
+ * the new claim data behind the claims that stay (rows x W, row-major): there is no second pass. With keep it writes W + 1
+ * words per row into a temporary of the call, and the kept rows are compacted over tiles of 1024 rows: per-tile counts, one
+ * workgroup that turns them into tile offsets and the total, and a scatter that recomputes each kept row's rank from wave
+ * ballots and copies whole claims with consecutive lanes on consecutive words; rows <= 1024 take the scatter alone. The three
+ * launches are ordered by the stream; no position depends on the order in which atomics land. Offsets are written on the
+ * device. Bytes per row: 8 (W + 1) written by the pass, the flag read twice, and 8 W read and 8 W written per kept row.
+ *   The new offset and data arrays, device and host copies, are built beside the witness's and change places with them as the
+ * last step. MS_ERR at any point - a refusal, an allocation failure, a non-canonical input - leaves the witness's claims and
+ * traces what they were and the context usable.
+ *   Host waits: at most two. One brings the inputs' offender word and the kept total in one read-back (not needed without
+ * inputs and without keep); one brings the host copy of the new claims, which the witness keeps for short transcripts (in
+ * chunks when the list is longer than the staging buffer).
+ *   MS_ERR (texts start "ms_witness_claims_fill: "): a witness of another system; a witness that holds only a slice of its
+ * claims; a host-resident witness; a witness with circuits held by another rank; mode neither 0 nor 1; a circuit out of range,
+ * inactive or without a trace on this device; a blob that ms_claims_program_info refuses; widths other than the circuit's; a
+ * preprocessed trace that is not on the device at this height; rows > n; n_inputs > 0 with inputs = NULL, an input height above
+ * n, an input matrix that fails the checks of ms_witness_create_device, an 8-byte input element >= p ("non-canonical input
+ * value: row 5, column 1"); a total of 2^60 elements or more. */
+#define MS_CLAIMS_REPLACE 0
+#define MS_CLAIMS_APPEND 1
+int32_t ms_witness_claims_fill(ms_system* sys, ms_witness* w, size_t circuit, const uint8_t* program, size_t program_len, size_t rows,
+                               const ms_dev_matrix* inputs /* nullable with n_inputs 0 */, void* producer_stream /* hipStream_t, nullable */,
+                               uint32_t mode, uint64_t summary[4]);
+/* Host code, no device: checks a claim program as ms_witness_claims_fill does (everything that needs no witness): out4 =
+ * [instructions per row, live slots, lanes per workgroup of the LDS form (0: global scratch), W | has_keep << 32]. MS_ERR: a
+ * wrong magic (a fill program is named as such); a length other than 7 + 3 n_nodes + W words; W = 0 or W > 2^16; an element
+ * root or the keep root out of range; every node refusal of ms_fill_program_info with "claim program" in its text; a peer
+ * source. Texts start "ms_claims_program_info: ". */
+int32_t ms_claims_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
+/* Diagnostic, in the manner of ms_witness_trace: the claims of a device-resident witness read back from the DEVICE copy, which
+ * is what the prover hashes for long lists. *n_claims and *n_elems are always set; offsets_out receives *n_claims + 1 words,
+ * data_out *n_elems. MS_ERR_BUFFER when cap_offsets < *n_claims + 1 or cap_data < *n_elems; nothing is written then.
+ * Host-resident witnesses and witnesses that hold a slice of their claims: MS_ERR. */
+int32_t ms_witness_claims(ms_witness* w, uint64_t* offsets_out, size_t cap_offsets, uint64_t* data_out, size_t cap_data, size_t* n_claims,
+                          size_t* n_elems);
+
 /* ---- The sorting permutation of a circuit's rows, made on the device. Indexed reads let a fill program write a sorted or
  * permuted copy of a column (sorted[r] = log[perm[r]]); this call produces perm, so that the witness of an offline memory
  * check, of a range check by sorted differences or of a permutation argument never leaves HBM: sort, gather, scan.

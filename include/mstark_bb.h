@@ -221,7 +221,8 @@ int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target
  * mul root, init] with strictly ascending step indices and init < p. Nodes that no step reaches are not subject to the
  * offset-1 rule in this format. Each call goes on refusing BOTH magics of the other field as a wrong magic.
  * msbb_witness_fill also refuses the third format of include/mstark.h ("PEER READS", magic "\0MFILL03") by its magic: this
- * configuration has no peer reads yet.
+ * configuration has no peer reads yet. Claim programs (ms_witness_claims_fill, "CLAIM PROGRAMS" there) are Goldilocks alone so
+ * far as well: claims here are Montgomery words on the device and canonical vectors on the host.
  *   Not part of this: accumulators over the degree-4 extension (four coupled columns that follow the previous row together,
  * as the running sum of a lookup argument over the challenge field) - a scan step is one base-field column.
  *   Execution: the groups in order on the context's stream - an ordinary group as above, a scan group as a coefficient pass

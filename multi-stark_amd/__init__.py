@@ -54,7 +54,8 @@ def exported_symbols():
             "ms_witness_commit_stage1", "ms_challenger_observe_claims", "ms_witness_claims_accumulator", "ms_stage2_build",
             "ms_pcs_commit_traces", "ms_quotient", "ms_pcs_commit_ldes", "ms_witness_check", "ms_system_check_info", "ms_witness_lookup_balance",
             "ms_system_multiplicity_slot", "ms_witness_derive_multiplicities", "ms_witness_fill", "ms_fill_program_info",
-            "ms_fill_scan_info", "ms_witness_argsort", "ms_sort_info", "ms_fill_peer_info"]
+            "ms_fill_scan_info", "ms_witness_argsort", "ms_sort_info", "ms_fill_peer_info", "ms_witness_claims_fill", "ms_claims_program_info",
+            "ms_witness_claims"]
 
 
 # ms_system_circuit_kernels / msbb_system_circuit_kernels (MS_KERNEL_* in include/mstark.h)
@@ -718,6 +719,32 @@ class FillReport:
         return "%d rows x %d steps: %d instructions per row, %s" % (self.rows, self.steps, self.instructions, form)
 
 
+CLAIMS_REPLACE, CLAIMS_APPEND = 0, 1  # MS_CLAIMS_* of include/mstark.h
+
+
+def claims_program_info(program):
+    """ms_claims_program_info (host only): checks a claim program (frontend.compile_claims, or its blob) and tells how
+    SystemWitness.fill_claims would run it -> {"instructions", "slots", "lds_lanes" (0: global scratch), "width", "has_keep"}"""
+    a, o = _program_bytes(program), np.zeros(4, dtype=np.uint64)
+    _check(lib().ms_claims_program_info(_b(a), C.c_size_t(a.size), _p(o)))
+    return {"instructions": int(o[0]), "slots": int(o[1]), "lds_lanes": int(o[2]), "width": int(o[3]) & 0xFFFFFFFF, "has_keep": bool(int(o[3]) >> 32)}
+
+
+class ClaimsReport:
+    """What SystemWitness.fill_claims returns: .rows (considered), .claims (emitted), .instructions (executed per row), .lds_lanes
+    (lanes per workgroup with the slot file in LDS; 0: the slots lay in a global scratch)"""
+
+    def __init__(self, rows, claims, instructions, lds_lanes):
+        self.rows, self.claims, self.instructions, self.lds_lanes = rows, claims, instructions, lds_lanes
+
+    def fields(self):
+        return (self.rows, self.claims, self.instructions, self.lds_lanes)
+
+    def __str__(self):
+        form = "slots in LDS at %d lanes" % self.lds_lanes if self.lds_lanes else "slots in a global scratch"
+        return "%d rows -> %d claims: %d instructions per row, %s" % (self.rows, self.claims, self.instructions, form)
+
+
 SORT_PERM, SORT_RANK = 0, 1  # MS_SORT_* of include/mstark.h
 
 
@@ -782,6 +809,46 @@ class SystemWitness:
         _check(lib().ms_witness_fill(self.h, C.c_size_t(circuit), _b(a), C.c_size_t(a.size), C.byref(mat) if mat is not None else None,
                                      _producer_stream(stream, seen), _p(summary)))
         return FillReport(*(int(x) for x in summary))
+
+    def fill_claims(self, circuit, program, rows=None, inputs=None, append=False, stream=None):
+        """ms_witness_claims_fill: the claims that `program` (frontend.compile_claims, or its blob) emits for rows [0, rows) of
+        `circuit` (default: its whole height), one per row the program keeps, built on the device from the traces; they replace the
+        witness's claims or, with append=True, follow them. inputs and stream as for fill. The traces are not touched. Pipeline
+        order: fill, fill_claims, derive_multiplicities, check, prove. -> ClaimsReport"""
+        a = _program_bytes(program)
+        mat, seen = None, None
+        if inputs is not None:
+            ptr, shape, strides, item, is_torch = _device_array(inputs, "fill_claims inputs")
+            if len(shape) != 2:
+                raise MstarkError("fill_claims inputs: expected a 2-D matrix, got %d dimension(s)" % len(shape))
+            (h, w), (rs, cs) = shape, strides
+            want = int(a[24:32].view("<u8")[0]) if a.size >= 56 else w  # the blob's n_inputs word (a shorter blob is refused below)
+            if w != want:
+                raise MstarkError("fill_claims inputs: width %d, the program reads %d input columns" % (w, want))
+            seen = inputs if is_torch else None
+            mat = DevMatrix(ptr or None, h, item, rs if h > 1 else max(w, 1), cs if w > 1 else 1)
+        if rows is None:
+            need = C.c_size_t()
+            rc = lib().ms_witness_trace(self.h, C.c_size_t(circuit), None, C.c_size_t(0), C.byref(need))
+            if rc != -3:
+                _check(rc)
+            rows = need.value // max(self.system.circuit_info(circuit)["main_width"], 1)
+        summary = np.zeros(4, dtype=np.uint64)
+        _check(lib().ms_witness_claims_fill(self.system.h, self.h, C.c_size_t(circuit), _b(a), C.c_size_t(a.size), C.c_size_t(rows),
+                                            C.byref(mat) if mat is not None else None, _producer_stream(stream, seen),
+                                            C.c_uint32(CLAIMS_APPEND if append else CLAIMS_REPLACE), _p(summary)))
+        return ClaimsReport(*(int(x) for x in summary))
+
+    def claims(self):
+        """the claims of a device-resident witness read back from the device (ms_witness_claims) -> (offsets: n_claims + 1
+        uint64, data: uint64); claim i is data[offsets[i]:offsets[i + 1]]"""
+        n, e = C.c_size_t(), C.c_size_t()
+        rc = lib().ms_witness_claims(self.h, None, C.c_size_t(0), None, C.c_size_t(0), C.byref(n), C.byref(e))
+        if rc != -3:  # (MS_ERR_BUFFER: the counts)
+            _check(rc)
+        offs, data = np.zeros(n.value + 1, dtype=np.uint64), np.zeros(e.value, dtype=np.uint64)
+        _check(lib().ms_witness_claims(self.h, _p(offs), C.c_size_t(offs.size), _p(data), C.c_size_t(data.size), C.byref(n), C.byref(e)))
+        return offs, data
 
     def derive_multiplicities(self, targets, entries=64):
         """ms_witness_derive_multiplicities: targets = [(circuit, lookup slot)], the provider slots whose multiplicity is one

@@ -433,6 +433,38 @@ int32_t ms_fill_peer_info(const uint8_t* program, size_t program_len, uint64_t* 
   return *n_peers > cap ? MS_ERR_BUFFER : MS_OK;
   MS_CATCH
 }
+int32_t ms_witness_claims_fill(ms_system* sys, ms_witness* w, size_t circuit, const uint8_t* program, size_t program_len, size_t rows,
+                               const ms_dev_matrix* inputs, void* producer_stream, uint32_t mode, uint64_t summary[4]) {
+  MS_TRY if (!sys || !w || !program || !summary) throw std::runtime_error("ms_witness_claims_fill: null argument");
+  HIP_CHECK(hipSetDevice(sys->sys->ctx->device));
+  witness_claims_fill(*sys->sys, *w->w, circuit, program, program_len, rows, inputs, producer_stream, mode, summary);
+  return MS_OK;
+  MS_CATCH
+}
+int32_t ms_claims_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]) {
+  MS_TRY if (!program || !out4) throw std::runtime_error("ms_claims_program_info: null argument");
+  claims_program_info(program, program_len, out4);
+  return MS_OK;
+  MS_CATCH
+}
+int32_t ms_witness_claims(ms_witness* w, uint64_t* offsets_out, size_t cap_offsets, uint64_t* data_out, size_t cap_data, size_t* n_claims,
+                          size_t* n_elems) {
+  MS_TRY if (!w || !n_claims || !n_elems) throw std::runtime_error("ms_witness_claims: null argument");
+  HWitness& wit = *w->w;
+  if (wit.claims_partial) throw std::runtime_error("ms_witness_claims: this witness holds only a slice of its claims (ms_witness_create_host_sliced)");
+  if (wit.host_resident) throw std::runtime_error("ms_witness_claims: a host-resident witness keeps its claims on the host between proofs");
+  *n_claims = wit.claim_offsets.size() - 1;
+  *n_elems = wit.claim_elems_total;
+  if (*n_claims + 1 > cap_offsets || *n_elems > cap_data) return MS_ERR_BUFFER;
+  if (!offsets_out || (*n_elems && !data_out)) throw std::runtime_error("ms_witness_claims: null output");
+  Ctx& ctx = *wit.sys->ctx;
+  HIP_CHECK(hipSetDevice(ctx.device));
+  if (!wit.d_claim_offsets.p) throw std::runtime_error("ms_witness_claims: the witness has no claims on this device");
+  ctx.d2h_queue(offsets_out, wit.d_claim_offsets.p, (*n_claims + 1) * 8);
+  ctx.d2h(data_out, wit.d_claim_data.p, *n_elems * 8);
+  return MS_OK;
+  MS_CATCH
+}
 int32_t ms_witness_argsort(ms_system* sys, ms_witness* w, size_t circuit, const uint32_t* key_columns, size_t n_keys, uint32_t dst_column,
                            uint32_t what, uint64_t summary[4]) {
   MS_TRY if (!sys || !w || !summary || (!key_columns && n_keys)) throw std::runtime_error("ms_witness_argsort: null argument");

@@ -150,7 +150,7 @@ void abandon_pending() {
 
 static const char* KNAMES[K_COUNT] = {"ntt_lds_strided", "ntt_lds_contig", "ntt12_dif", "ntt12_dit", "ntt8s_dif", "ntt8s_dit", "leaf_hash", "compress_layer", "stage2", "quotient",
                                       "bary_eval",   "deep_reduce", "fri_fold", "transpose",      "other",       "witness_check",
-                                      "witness_argsort"};
+                                      "witness_argsort", "witness_claims"};
 const char* kernel_name(int id) { return id >= 0 && id < K_COUNT ? KNAMES[id] : "?"; }
 
 namespace {

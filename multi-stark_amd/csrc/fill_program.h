@@ -27,6 +27,12 @@
 // records n_peers records [circuit, trace, width]. Source byte 4 + k of a variable or an `at` names record k, whose width bounds
 // the column. The call never writes a peer, so such a node has deps = 0, keeps one instance per pass and falls under no group
 // rule; the source travels in the immediates as it stands. Apart from that the format is the second: groups, 0 scans allowed.
+//
+// CLAIM PROGRAMS (ms_witness_claims_fill; magic "\0MCLAIM1", a format of its own): W element roots and an optional keep root over
+// the same nodes, no steps. claims_compile reads and checks the nodes with the functions fill_compile uses (fill_read_nodes,
+// fill_check_nodes: one text and one order of refusals), without the rules of assigned columns - nothing is assigned, so every
+// main column may be read at the next row or at a computed row - and with peer sources refused; it linearises ONE pass with
+// bind = false, as a scan's coefficient pass is: outputs 0 .. W - 1 are the elements, output W the keep flag.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -47,9 +53,11 @@ struct FillField {
   unsigned value_bits;  // bits(x, lo, length) needs lo + length <= value_bits
   uint64_t scan_magic;  // the first word of a program with scan steps; 0: this configuration has none
   uint64_t peer_magic;  // the first word of a program with peer reads (the third format); 0: this configuration has none
+  uint64_t claim_magic; // the first word of a claim program (claims_compile); 0: this configuration has none
 };
-constexpr FillField FILL_GOLDILOCKS{0x31304C4C49464D00ull, 0xFFFFFFFF00000001ull, 64, 0x32304C4C49464D00ull, 0x33304C4C49464D00ull};  // "\0MFILL01", "\0MFILL02", "\0MFILL03"
-constexpr FillField FILL_BABYBEAR{0x3130424C49464D00ull, 0x78000001ull, 32, 0x3230424C49464D00ull, 0};                                // "\0MFILB01", "\0MFILB02"
+constexpr FillField FILL_GOLDILOCKS{0x31304C4C49464D00ull, 0xFFFFFFFF00000001ull, 64, 0x32304C4C49464D00ull, 0x33304C4C49464D00ull,
+                                    0x314D49414C434D00ull};                                                 // "\0MFILL01", "\0MFILL02", "\0MFILL03", "\0MCLAIM1"
+constexpr FillField FILL_BABYBEAR{0x3130424C49464D00ull, 0x78000001ull, 32, 0x3230424C49464D00ull, 0, 0};  // "\0MFILB01", "\0MFILB02"
 
 constexpr uint32_t FL_NONE = ~0u;
 constexpr uint32_t FL_SRC_PRE = 0, FL_SRC_MAIN = 1, FL_SRC_INPUT = 3, FL_SRC_PEER = 4;  // source 4 + k: peer k of the program
@@ -207,6 +215,96 @@ inline FillPass fill_linearise(const std::vector<PNode>& nodes, const std::vecto
   return out;
 }
 
+// The n_nodes nodes of a blob, three words each from word `first` on (rd(i): word i; the caller has checked the length).
+template <class Rd, class Fail>
+inline std::vector<PNode> fill_read_nodes(const Rd& rd, size_t first, size_t nn, const Fail& fail) {
+  std::vector<PNode> nodes(nn);
+  for (size_t i = 0; i < nn; i++) {
+    const uint64_t head = rd(first + 3 * i);
+    if (head >> 24) fail("node " + std::to_string(i) + ": malformed head word");
+    nodes[i].kind = (uint32_t)(head & 0xff), nodes[i].source = (uint32_t)((head >> 8) & 0xff), nodes[i].offset = (uint32_t)(head >> 16);
+    nodes[i].a = rd(first + 1 + 3 * i), nodes[i].b = rd(first + 2 + 3 * i);
+  }
+  return nodes;
+}
+
+inline std::string fill_peer_name(const std::vector<FillPeer>& peers, size_t k) {
+  return "peer " + std::to_string(k) + " (circuit " + std::to_string(peers[k].circuit) + ", " + (peers[k].trace ? "main" : "preprocessed") + " trace)";
+}
+
+// Every node against the widths, the field and the peer records, in node order -> deps: the node reads, directly or through
+// operands, a main column at offset 0. assigned (nullable): the columns a program of ONE group assigns, which may be read
+// neither at the next row nor at a computed row (the first format; the second and third apply the rule by groups, behind this).
+// claims: a claim program - its name in the texts, peer sources refused, nothing assigned.
+template <class Fail>
+inline std::vector<char> fill_check_nodes(const std::vector<PNode>& nodes, const FillField& field, uint64_t main_w, uint64_t pre_w, uint64_t n_in,
+                                          const std::vector<FillPeer>& peers, const std::vector<char>* assigned, bool claims, const Fail& fail) {
+  typedef uint64_t u64;
+  const size_t nn = nodes.size(), npeer = peers.size();
+  const std::string program = claims ? "claim" : "fill";
+  auto peer_name = [&](size_t k) { return fill_peer_name(peers, k); };
+  auto known_source = [&](uint32_t s) { return s == FL_SRC_PRE || s == FL_SRC_MAIN || s == FL_SRC_INPUT || (s >= FL_SRC_PEER && s - FL_SRC_PEER < npeer); };
+  auto claims_peer = [&](uint32_t s) { return claims && s >= FL_SRC_PEER && s - FL_SRC_PEER < FL_MAX_PEERS; };
+  std::vector<char> deps(nn, 0);  // reads, directly or through operands, a main column at offset 0
+  for (size_t i = 0; i < nn; i++) {
+    const PNode& n = nodes[i];
+    const std::string at = "node " + std::to_string(i) + ": ";
+    if (n.kind == OP_CONST) {
+      if (n.a >= field.modulus) fail(at + "non-canonical constant");
+    } else if (n.kind == OP_VAR) {
+      if (n.source == 2) fail(at + "stage-2 variables are not allowed in a " + program + " program");
+      if (claims_peer(n.source)) fail(at + "peer reads are not allowed in a claim program (source " + std::to_string(n.source) + ")");
+      if (!known_source(n.source)) fail(at + "unknown variable source");
+      if (n.offset > 1) fail(at + "row offset out of range");
+      if (n.source >= FL_SRC_PEER) {
+        const size_t k = n.source - FL_SRC_PEER;
+        if (n.a >= peers[k].width) fail(at + "variable " + std::to_string(n.a) + " of " + peer_name(k) + " is out of range (width " + std::to_string(peers[k].width) + ")");
+        continue;  // (deps = 0: the call writes no peer)
+      }
+      const u64 width = n.source == FL_SRC_PRE ? pre_w : n.source == FL_SRC_MAIN ? main_w : n_in;
+      if (n.a >= width) fail(at + "variable " + std::to_string(n.a) + " of source " + std::to_string(n.source) + " is out of range (width " + std::to_string(width) + ")");
+      if (assigned && n.source == FL_SRC_MAIN && n.offset == 1 && (*assigned)[n.a])  // (the second format: by groups, in fill_compile)
+        fail(at + "offset-1 read of main column " + std::to_string(n.a) + ", which the program assigns (the next row may be read only of columns no step assigns)");
+      deps[i] = n.source == FL_SRC_MAIN && n.offset == 0;
+    } else if (n.kind == OP_AT) {
+      if (n.source == 2) fail(at + "stage-2 columns are not allowed in a " + program + " program");
+      if (claims_peer(n.source)) fail(at + "peer reads are not allowed in a claim program (source " + std::to_string(n.source) + ")");
+      if (!known_source(n.source)) fail(at + "unknown source of an indexed read");
+      const bool peer = n.source >= FL_SRC_PEER;
+      const u64 width = peer ? peers[n.source - FL_SRC_PEER].width : n.source == FL_SRC_PRE ? pre_w : n.source == FL_SRC_MAIN ? main_w : n_in;
+      if (n.offset) fail(at + "the offset field of an indexed read must be 0");
+      if (peer && n.a >= width)
+        fail(at + "indexed read of column " + std::to_string(n.a) + " of " + peer_name(n.source - FL_SRC_PEER) + ", which is out of range (width " + std::to_string(width) + ")");
+      if (n.a >= width)
+        fail(at + "indexed read of column " + std::to_string(n.a) + " of source " + std::to_string(n.source) + ", which is out of range (width " + std::to_string(width) + ")");
+      if (n.b >= i) fail(at + "forward row operand");
+      if (assigned && n.source == FL_SRC_MAIN && (*assigned)[n.a])  // (one group; the second format: by groups, in fill_compile)
+        fail(at + "indexed read of main column " + std::to_string(n.a) +
+             " by step group 0, which step group 0 assigns (a computed row may be read only of columns that no step of the same or a later group assigns)");
+      deps[i] = deps[n.b];
+    } else if (n.kind == OP_PUBLIC) {
+      fail(at + "publics are not allowed in a " + program + " program");
+    } else if (n.kind == OP_IS_FIRST || n.kind == OP_IS_LAST || n.kind == OP_IS_TRANS) {
+      fail(at + "selector nodes are not allowed in a " + program + " program (they are polynomials, not flags: use row, lt and inv0)");
+    } else if (n.kind == OP_ROW) {
+    } else if (fl_unary(n.kind)) {
+      if (n.a >= i) fail(at + "forward operand");
+      if (n.kind == OP_BITS) {
+        const u64 lo = n.b & 0xff, length = n.b >> 8;
+        if ((n.b >> 16) || length < 1 || lo + length > field.value_bits)
+          fail(at + "bad bits fields (need 1 <= length and lo + length <= " + std::to_string(field.value_bits) + ")");
+      }
+      deps[i] = deps[n.a];
+    } else if (fl_binary(n.kind)) {
+      if (n.a >= i || n.b >= i) fail(at + "forward operand");
+      deps[i] = deps[n.a] | deps[n.b];
+    } else {
+      fail(at + "unknown node kind " + std::to_string(n.kind));
+    }
+  }
+  return deps;
+}
+
 inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string& name, const FillField& field) {
   typedef uint64_t u64;
   auto fail = [&](const std::string& what) -> void { throw std::runtime_error(name + ": " + what); };
@@ -230,13 +328,7 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
     fail("truncated program blob: " + std::to_string(nw) + " words for " + std::to_string(nn) + " nodes and " + std::to_string(ns) + " steps" +
          (v2 ? " and " + std::to_string(nsc) + " scans" : std::string()) + (v3 ? " and " + std::to_string(npeer) + " peers" : std::string()));
   if (nn > FL_MAX_NODES) fail("more than 2^24 nodes");
-  std::vector<PNode> nodes(nn);
-  for (size_t i = 0; i < nn; i++) {
-    const u64 head = rd(hw + 3 * i);
-    if (head >> 24) fail("node " + std::to_string(i) + ": malformed head word");
-    nodes[i].kind = (uint32_t)(head & 0xff), nodes[i].source = (uint32_t)((head >> 8) & 0xff), nodes[i].offset = (uint32_t)(head >> 16);
-    nodes[i].a = rd(hw + 1 + 3 * i), nodes[i].b = rd(hw + 2 + 3 * i);
-  }
+  const std::vector<PNode> nodes = fill_read_nodes(rd, hw, nn, fail);
   std::vector<std::pair<uint32_t, uint32_t>> steps(ns);
   std::vector<char> assigned(main_w, 0);
   const size_t s0 = hw + 3 * nn;
@@ -267,9 +359,7 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
   // peer records [circuit, trace, width], no (circuit, trace) twice
   std::vector<FillPeer> peers(npeer);
   const size_t p0 = c0 + 3 * nsc;
-  auto peer_name = [&](size_t k) {
-    return "peer " + std::to_string(k) + " (circuit " + std::to_string(peers[k].circuit) + ", " + (peers[k].trace ? "main" : "preprocessed") + " trace)";
-  };
+  auto peer_name = [&](size_t k) { return fill_peer_name(peers, k); };
   for (size_t k = 0; k < npeer; k++) {
     peers[k] = FillPeer{rd(p0 + 3 * k), rd(p0 + 3 * k + 1), rd(p0 + 3 * k + 2)};
     const std::string at = "peer " + std::to_string(k) + ": ";
@@ -279,62 +369,7 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
     for (size_t j = 0; j < k; j++)
       if (peers[j].circuit == peers[k].circuit && peers[j].trace == peers[k].trace) fail(at + "the same circuit and trace as peer " + std::to_string(j) + " (" + peer_name(j) + ")");
   }
-  auto known_source = [&](uint32_t s) { return s == FL_SRC_PRE || s == FL_SRC_MAIN || s == FL_SRC_INPUT || (s >= FL_SRC_PEER && s - FL_SRC_PEER < npeer); };
-  std::vector<char> deps(nn, 0);  // reads, directly or through operands, a main column at offset 0
-  for (size_t i = 0; i < nn; i++) {
-    const PNode& n = nodes[i];
-    const std::string at = "node " + std::to_string(i) + ": ";
-    if (n.kind == OP_CONST) {
-      if (n.a >= field.modulus) fail(at + "non-canonical constant");
-    } else if (n.kind == OP_VAR) {
-      if (n.source == 2) fail(at + "stage-2 variables are not allowed in a fill program");
-      if (!known_source(n.source)) fail(at + "unknown variable source");
-      if (n.offset > 1) fail(at + "row offset out of range");
-      if (n.source >= FL_SRC_PEER) {
-        const size_t k = n.source - FL_SRC_PEER;
-        if (n.a >= peers[k].width) fail(at + "variable " + std::to_string(n.a) + " of " + peer_name(k) + " is out of range (width " + std::to_string(peers[k].width) + ")");
-        continue;  // (deps = 0: the call writes no peer)
-      }
-      const u64 width = n.source == FL_SRC_PRE ? pre_w : n.source == FL_SRC_MAIN ? main_w : n_in;
-      if (n.a >= width) fail(at + "variable " + std::to_string(n.a) + " of source " + std::to_string(n.source) + " is out of range (width " + std::to_string(width) + ")");
-      if (!v2 && n.source == FL_SRC_MAIN && n.offset == 1 && assigned[n.a])  // (the second format: by groups, below)
-        fail(at + "offset-1 read of main column " + std::to_string(n.a) + ", which the program assigns (the next row may be read only of columns no step assigns)");
-      deps[i] = n.source == FL_SRC_MAIN && n.offset == 0;
-    } else if (n.kind == OP_AT) {
-      if (n.source == 2) fail(at + "stage-2 columns are not allowed in a fill program");
-      if (!known_source(n.source)) fail(at + "unknown source of an indexed read");
-      const bool peer = n.source >= FL_SRC_PEER;
-      const u64 width = peer ? peers[n.source - FL_SRC_PEER].width : n.source == FL_SRC_PRE ? pre_w : n.source == FL_SRC_MAIN ? main_w : n_in;
-      if (n.offset) fail(at + "the offset field of an indexed read must be 0");
-      if (peer && n.a >= width)
-        fail(at + "indexed read of column " + std::to_string(n.a) + " of " + peer_name(n.source - FL_SRC_PEER) + ", which is out of range (width " + std::to_string(width) + ")");
-      if (n.a >= width)
-        fail(at + "indexed read of column " + std::to_string(n.a) + " of source " + std::to_string(n.source) + ", which is out of range (width " + std::to_string(width) + ")");
-      if (n.b >= i) fail(at + "forward row operand");
-      if (!v2 && n.source == FL_SRC_MAIN && assigned[n.a])  // (one group; the second format: by groups, below)
-        fail(at + "indexed read of main column " + std::to_string(n.a) +
-             " by step group 0, which step group 0 assigns (a computed row may be read only of columns that no step of the same or a later group assigns)");
-      deps[i] = deps[n.b];
-    } else if (n.kind == OP_PUBLIC) {
-      fail(at + "publics are not allowed in a fill program");
-    } else if (n.kind == OP_IS_FIRST || n.kind == OP_IS_LAST || n.kind == OP_IS_TRANS) {
-      fail(at + "selector nodes are not allowed in a fill program (they are polynomials, not flags: use row, lt and inv0)");
-    } else if (n.kind == OP_ROW) {
-    } else if (fl_unary(n.kind)) {
-      if (n.a >= i) fail(at + "forward operand");
-      if (n.kind == OP_BITS) {
-        const u64 lo = n.b & 0xff, length = n.b >> 8;
-        if ((n.b >> 16) || length < 1 || lo + length > field.value_bits)
-          fail(at + "bad bits fields (need 1 <= length and lo + length <= " + std::to_string(field.value_bits) + ")");
-      }
-      deps[i] = deps[n.a];
-    } else if (fl_binary(n.kind)) {
-      if (n.a >= i || n.b >= i) fail(at + "forward operand");
-      deps[i] = deps[n.a] | deps[n.b];
-    } else {
-      fail(at + "unknown node kind " + std::to_string(n.kind));
-    }
-  }
+  const std::vector<char> deps = fill_check_nodes(nodes, field, main_w, pre_w, n_in, peers, v2 ? nullptr : &assigned, false, fail);
 
   FillCode out;
   out.main_w = main_w, out.pre_w = pre_w, out.n_inputs = n_in, out.n_steps = ns, out.n_scans = nsc;
@@ -408,6 +443,58 @@ inline FillCode fill_compile(const uint8_t* blob, size_t len, const std::string&
     out.groups.push_back(std::move(gr));
   }
   out.n_slots = std::max<size_t>(out.n_slots, 1);
+  return out;
+}
+
+// ---- claim programs
+constexpr size_t CL_MAX_WIDTH = size_t(1) << 16;  // elements of one claim
+struct ClaimCode {
+  FillPass pass;  // outs: (e, slot) for the elements e = 0 .. W - 1 and, with a keep root, (W, slot of the keep flag)
+  size_t main_w = 0, pre_w = 0, n_inputs = 0, width = 0;
+  bool has_keep = false;
+};
+
+// [magic, main_width, pre_width, n_inputs, n_nodes, W, keep root (all ones: none)], the nodes, the W element roots.
+inline ClaimCode claims_compile(const uint8_t* blob, size_t len, const std::string& name, const FillField& field) {
+  typedef uint64_t u64;
+  auto fail = [&](const std::string& what) -> void { throw std::runtime_error(name + ": " + what); };
+  if (!field.claim_magic) fail("this configuration has no claim programs");
+  if (!blob) fail("null program");
+  const size_t hw = 7;
+  if (len % 8 || len < 8 * hw) fail("truncated program blob (" + std::to_string(len) + " bytes)");
+  const size_t nw = len / 8;
+  auto rd = [&](size_t i) {
+    u64 v;
+    memcpy(&v, blob + 8 * i, 8);
+    return v;
+  };
+  if (rd(0) == field.magic || (field.scan_magic && rd(0) == field.scan_magic) || (field.peer_magic && rd(0) == field.peer_magic))
+    fail("a fill program, not a claim program (a claim program assigns nothing, has no scan steps and reads no peer; its magic is another)");
+  if (rd(0) != field.claim_magic) fail("not a claim program (wrong magic)");
+  const u64 main_w = rd(1), pre_w = rd(2), n_in = rd(3), nn = rd(4), W = rd(5), keep = rd(6);
+  if (main_w > FL_MAX_WIDTH || pre_w > FL_MAX_WIDTH || n_in > FL_MAX_WIDTH) fail("widths out of range");
+  if (W < 1 || W > CL_MAX_WIDTH) fail("a claim has 1 to 2^16 elements, this program " + std::to_string(W));
+  if (nn > nw / 3 || hw + 3 * nn + W != nw)
+    fail("truncated program blob: " + std::to_string(nw) + " words for " + std::to_string(nn) + " nodes and " + std::to_string(W) + " elements");
+  if (nn > FL_MAX_NODES) fail("more than 2^24 nodes");
+  const std::vector<PNode> nodes = fill_read_nodes(rd, hw, nn, fail);
+  std::vector<std::pair<uint32_t, uint32_t>> outs(W);
+  const size_t e0 = hw + 3 * nn;
+  for (size_t e = 0; e < W; e++) {
+    const u64 root = rd(e0 + e);
+    if (root >= nn) fail("element " + std::to_string(e) + ": root " + std::to_string(root) + " is out of range");
+    outs[e] = {(uint32_t)e, (uint32_t)root};
+  }
+  const bool has_keep = keep != ~u64(0);
+  if (has_keep) {
+    if (keep >= nn) fail("keep: root " + std::to_string(keep) + " is out of range");
+    outs.push_back({(uint32_t)W, (uint32_t)keep});
+  }
+  fill_check_nodes(nodes, field, main_w, pre_w, n_in, std::vector<FillPeer>(), nullptr, true, fail);
+  ClaimCode out;
+  out.main_w = main_w, out.pre_w = pre_w, out.n_inputs = n_in, out.width = W, out.has_keep = has_keep;
+  // nothing is assigned, so no node's value changes from output to output: deps = 0 throughout, each node is one instance
+  out.pass = fill_linearise(nodes, std::vector<char>(nn, 0), outs, W + has_keep, false, fail);
   return out;
 }
 

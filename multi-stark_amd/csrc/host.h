@@ -242,6 +242,12 @@ void fill_program_info(const uint8_t* program, size_t program_len, u64 out4[4]);
 void fill_scan_info(const uint8_t* program, size_t program_len, u64 out4[4]);
 // ms_fill_peer_info: host only - the peer records [circuit, trace, width] into out (written when they fit cap) -> their number
 size_t fill_peer_info(const uint8_t* program, size_t program_len, u64* out, size_t cap);
+// ms_witness_claims_fill (fill.hip): the claims a claim program emits for the first `rows` rows of circuit `ci`, in place of the
+// witness's claims or behind them. At most two host waits: the inputs' offender word with the kept total, and the host copy
+void witness_claims_fill(HSystem& sys, HWitness& wit, size_t ci, const uint8_t* program, size_t program_len, size_t rows, const ms_dev_matrix* inputs,
+                         void* producer_stream, uint32_t mode, u64 summary[4]);
+// ms_claims_program_info: host only - [instructions, live slots, lanes of the LDS form (0: global scratch), W | has_keep << 32]
+void claims_program_info(const uint8_t* program, size_t program_len, u64 out4[4]);
 // ms_witness_argsort (argsort.hip): the stable sorting permutation of circuit `ci`'s rows under the key columns (or its inverse,
 // what = 1) written into main column dst; held lookup values of the circuit follow. One host wait: the digit histograms
 void witness_argsort(HSystem& sys, HWitness& wit, size_t ci, const uint32_t* key_columns, size_t n_keys, uint32_t dst, uint32_t what,

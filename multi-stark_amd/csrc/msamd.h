@@ -51,6 +51,7 @@ enum KernelId : int {
   K_OTHER,
   K_WITNESS_CHECK,    // constraint roots on the trace domain (check_dev.h, ms_witness_check / msbb_witness_check)
   K_WITNESS_ARGSORT,  // the launches of ms_witness_argsort behind its host wait (argsort.hip: extraction, digit passes, final write)
+  K_WITNESS_CLAIMS,   // the compaction launches of ms_witness_claims_fill (claims_dev.h: counts, offsets, scatter), not its evaluation pass
   K_COUNT
 };
 const char* kernel_name(int id);

@@ -33,6 +33,8 @@ FILL_MAGIC = 0x31304C4C49464D00  # "\0MFILL01"; over BabyBear "\0MFILB01": a fil
 FILL_BITS = 64  # bits(x, lo, length) needs lo + length <= the width of a value: 64, over BabyBear 32
 FILL_SCAN_MAGIC = 0x32304C4C49464D00  # "\0MFILL02": a program with scan steps; over BabyBear "\0MFILB02"
 FILL_PEER_MAGIC = 0x33304C4C49464D00  # "\0MFILL03": a program with peer reads (Goldilocks alone)
+CLAIM_MAGIC = 0x314D49414C434D00  # "\0MCLAIM1": a claim program (compile_claims, ms_witness_claims_fill; Goldilocks alone so far)
+CLAIM_MAX_WIDTH = 1 << 16
 SRC_PEER, FL_MAX_PEERS = 4, 8  # source byte 4 + k: peer record k of the program (include/mstark.h, "PEER READS")
 
 # The two StarkGenericConfig instantiations of the reference: GoldilocksBlake3Config (src/types.rs:24-29,199-223) and
@@ -680,6 +682,8 @@ class _FillInterner(_Interner):
         """the width a column of `source` must stay below; a peer: from compile_fill's peers= ({circuit: (main, preprocessed)})"""
         if isinstance(source, tuple):
             _, circuit, trace = source
+            if spec.get("claims"):
+                raise CompileError("PeerReadInClaimProgram circuit=%d: a claim program reads the traces of its own circuit and the inputs" % circuit)
             if FILL_MAGIC != GOLDILOCKS["FILL_MAGIC"]:
                 raise CompileError("PeerReadInThisField circuit=%d: peer reads: Goldilocks configuration only" % circuit)
             if circuit not in (spec["peers"] or {}):
@@ -950,6 +954,65 @@ def rows_per_item_fill_program(k):
             sel = sel * (bit[t] if (j >> t) & 1 else 1 - bit[t])
         limb = limb + sel * bits(Expr.input_at(j >> 1, item), 8 * (j & 1), 8)
     return compile_fill(3, 0, max(k // 2, 1), [(0, item), (1, which), (2, limb)])
+
+
+# --------------------------------------------------------------------------- claim programs (ms_witness_claims_fill)
+# The claims of a witness as a function of one circuit's rows: W expressions, the elements of a claim, and optionally `keep`; one
+# claim per row of the first `rows` whose keep is non-zero, in row order. The algebra is that of fill programs without peer reads
+# and scans; nothing is assigned, so any main column may be read at the next row or at a computed row (include/mstark.h,
+# "CLAIM PROGRAMS").
+def claims_blob(main_width, preprocessed_width, n_inputs, nodes, roots, keep=None):
+    """The little-endian u64-word blob of a claim program, unchecked: magic, main_width, pre_width, n_inputs, n_nodes, W, the keep
+    root (all ones: none), the nodes as in fill_blob, the W element roots."""
+    words = [CLAIM_MAGIC, main_width, preprocessed_width, n_inputs, len(nodes), len(roots), (1 << 64) - 1 if keep is None else keep]
+    for (kind, source, offset, a, b) in nodes:
+        words += [kind | (source << 8) | (offset << 16), a, b]
+    words += list(roots)
+    return np.asarray(words, dtype=np.uint64).tobytes()
+
+
+class ClaimProgram:
+    """What compile_claims returns: .nodes (kind, source, offset, a, b), .roots (one per element), .keep (a root or None), the
+    widths, .width (W), .has_keep and .blob"""
+
+    def __init__(self, main_width, preprocessed_width, n_inputs, nodes, roots, keep=None):
+        self.main_width, self.preprocessed_width, self.n_inputs = main_width, preprocessed_width, n_inputs
+        self.nodes, self.roots, self.keep = nodes, list(roots), keep
+        self.width, self.has_keep = len(self.roots), keep is not None
+        self.blob = claims_blob(main_width, preprocessed_width, n_inputs, nodes, self.roots, keep)
+
+
+def compile_claims(main_width, preprocessed_width, n_inputs, elements, keep=None):
+    """elements: the W expressions of one claim, 1 <= W <= 2^16; keep: None (every row emits a claim) or an expression (the rows
+    where it is non-zero do). -> ClaimProgram"""
+    if FILL_MAGIC != GOLDILOCKS["FILL_MAGIC"]:
+        raise CompileError("ClaimProgramInThisField: claim programs: Goldilocks configuration only")
+    spec = {"main_width": int(main_width), "preprocessed_width": int(preprocessed_width), "n_inputs": int(n_inputs), "peers": None, "claims": True}
+    elements = list(elements)
+    if not 1 <= len(elements) <= CLAIM_MAX_WIDTH:
+        raise CompileError("ClaimWidthOutOfRange width=%d: a claim has 1 to 2^16 elements" % len(elements))
+    it = _FillInterner()
+
+    def root(e, what):
+        if isinstance(e, Scan):
+            raise CompileError("ScanInClaimProgram %s: a claim is a function of one row's reads, scan steps belong to fill programs" % what)
+        try:
+            return it.compile_fill_expr(Expr.lift(e), spec)
+        except CompileError as err:
+            raise CompileError("%s (%s of the claim program)" % (err, what)) from None
+
+    roots = [root(e, "element %d" % k) for k, e in enumerate(elements)]
+    keep_root = None if keep is None else root(keep, "keep")
+    return ClaimProgram(spec["main_width"], spec["preprocessed_width"], spec["n_inputs"], it.nodes, roots, keep_root)
+
+
+def u32_add_claims_program():
+    """The claims of the U32Add circuit (u32_add_system_inputs) from its filled trace, [1, x, y, z] per addition with the words
+    put together from their byte columns: call it with rows = the number of additions."""
+    def word(i):
+        return sum((Expr.main(i + k) * Expr.const(256 ** k) for k in range(1, 4)), Expr.main(i))
+
+    return compile_claims(14, 0, 0, [Expr.const(1), word(0), word(4), word(8)])
 
 
 # --------------------------------------------------------------------------- circuits

@@ -43,6 +43,14 @@ permutation, B the same two columns and the column that is written. One-step pro
 thread's row (peer), A's value through the permutation (peer_at), the same two reads of B's own columns (main, main_at), and
 the host route the peer reads replace - ms_witness_trace of A, the upload of that matrix, and input_at through the permutation.
 Each result is compared with numpy.
+  python tools/witness_fill.py --claims [--log-size 20] [--reps 9]
+--claims: the claims of the bench workload, [1, x, y, z] per addition, built on the device from the filled trace
+(ms_witness_claims_fill with frontend.u32_add_claims_program). The routes alternate: fill_claims alone without a keep expression
+(the pass writes the claims where they stay) and with an all-ones keep (the activity column: every row is kept, so the compaction
+moves the most it can); the whole device route, fill + fill_claims + derive_multiplicities; the host route it replaces -
+ms_witness_trace, numpy, and a new ms_witness_create_device from the traces in HBM with the claims given by the host; and the
+hand-written generator. The compaction's time is the difference of the two fill_claims lines, printed next to the bytes its
+layout states (8 (W + 1) written and read and 8 W written per kept row); it is no share of a peak.
 Timing: wall time of each route (all return synchronised), alternating after two warm-up rounds; median, minimum and maximum are
 printed. No figure here is a share of peak."""
 import argparse
@@ -65,6 +73,7 @@ ap.add_argument("--reps", type=int, default=9)
 ap.add_argument("--scan", action="store_true", help="the scan-step leg (both configurations)")
 ap.add_argument("--gather", action="store_true", help="the indexed-read leg (both configurations)")
 ap.add_argument("--peers", action="store_true", help="the peer-read leg (Goldilocks)")
+ap.add_argument("--claims", action="store_true", help="ms_witness_claims_fill on the bench workload (Goldilocks)")
 ap.add_argument("--alone", action="store_true", help="ms_witness_fill of U32Add alone in the process (Goldilocks)")
 args = ap.parse_args()
 
@@ -469,6 +478,107 @@ def alone_leg():
     del w
 
 
+def claims_leg():
+    """--claims: what building the claims on the device costs, next to the host round trip it replaces"""
+    E = fe.Expr
+    system = pkg.System.new(ctx, fe.bench_params(), fe.u32_add_system_inputs())
+    xs, ys = fe.xorshift_pairs(n)
+    traces, claims = fe._u32_add_traces(xs, ys, n)
+    packed = fe.pack_claims(claims)
+    fill_prog, plain = fe.u32_add_fill_program(n), fe.u32_add_claims_program()
+    word = lambda i: sum((E.main(i + k) * E.const(256 ** k) for k in range(1, 4)), E.main(i))
+    kept = fe.compile_claims(14, 0, 0, [E.const(1), word(0), word(4), word(8)], keep=E.main(13))
+    for name, p in (("without keep", plain), ("keep = the activity column", kept)):
+        print("claim program %-28s %d nodes; %s" % (name + ":", len(p.nodes), pkg.claims_program_info(p)))
+    pairs = torch.from_numpy(np.stack([xs, ys], axis=1).astype(np.uint32).view(np.int32)).cuda()
+    zeros = lambda: [torch.zeros(t.shape, dtype=torch.int64, device="cuda") for t in traces]
+    w = system.witness_from_device(zeros(), fe.pack_claims([]))
+    w.fill(1, fill_prog, pairs)
+    for p in (kept, plain):
+        rep = w.fill_claims(1, p, rows=n)
+        offs, data = w.claims()
+        same = bool(np.array_equal(offs, packed[0])) and bool(np.array_equal(data, packed[1]))
+        print("2^%d additions, %s: %s; claims equal the host builder's: %s" % (args.log_size, "with keep" if p.has_keep else "without keep", rep, same), flush=True)
+        assert same
+    dm = w.derive_multiplicities(TARGETS)
+    gen = system.bench_witness_on_device(n)
+    proof = system.prove_multiple_claims(w).to_bytes()
+    same_proof = proof == system.prove_multiple_claims(gen).to_bytes()
+    g = gen.claims()
+    same_gen = bool(np.array_equal(g[0], packed[0])) and bool(np.array_equal(g[1], packed[1]))
+    print("proof equals the generator's witness's: %s; the generator's claims are the same: %s; check().verdict: %d" % (same_proof, same_gen, w.check().verdict),
+          flush=True)
+    assert dm.ok and same_proof and same_gen
+    del gen
+    on_dev = [torch.from_numpy(np.ascontiguousarray(t).view(np.int64)).cuda() for t in traces]  # the host route's traces stay in HBM
+
+    print("\n# goldilocks, 2^%d additions: the routes, alternating" % args.log_size)
+    state = {}
+
+    def claims_alone(p):
+        def run():
+            w.fill_claims(1, p, rows=n)  # (returns synchronised: its last step is the host copy)
+        return run
+
+    def device_route():
+        w.fill(1, fill_prog, pairs)
+        w.fill_claims(1, plain, rows=n)
+        w.derive_multiplicities(TARGETS)
+
+    def host_read():
+        state["t"] = w.trace(1)
+
+    def host_numpy():
+        t = state["t"]
+        word = lambda i: t[:, i] | (t[:, i + 1] << np.uint64(8)) | (t[:, i + 2] << np.uint64(16)) | (t[:, i + 3] << np.uint64(24))
+        state["claims"] = fe.pack_claims(np.stack([np.ones(n, dtype=np.uint64), word(0), word(4), word(8)], axis=1))
+
+    def host_create():
+        state["host"] = None  # (the previous witness's memory goes back first)
+        state["host"] = system.witness_from_device(on_dev, state["claims"])
+
+    def generator():
+        state["gen"] = None
+        state["gen"] = system.bench_witness_on_device(n)
+        ctx.sync()
+
+    t_pl, t_kp, t_dev, t_rd, t_np, t_cr, t_gen = timed([claims_alone(plain), claims_alone(kept), device_route, host_read, host_numpy, host_create, generator],
+                                                       args.reps)
+    line("fill_claims alone, without keep", t_pl)
+    line("fill_claims alone, keep = all ones", t_kp)
+    line("device route: fill + fill_claims + derive", t_dev)
+    line("host: ms_witness_trace", t_rd)
+    line("host: numpy (the words from their bytes, pack)", t_np)
+    line("host: ms_witness_create_device, host claims", t_cr)
+    total = [a + b + c for a, b, c in zip(t_rd, t_np, t_cr)]
+    line("host route, the three steps together", total)
+    line("generator: ms_witness_u32_add_bench", t_gen)
+    m = statistics.median
+    W = plain.width
+    stated = n * (2 * 8 * (W + 1) + 8 * W)
+    print("host route / fill_claims = %.1f; device route / generator = %.2f" % (m(total) / m(t_pl), m(t_dev) / m(t_gen)))
+    # the compaction by itself: its launches between two events (the profile class witness_claims), one call at a time
+    ctx.set_profile(["witness_claims"])
+    t_cp = []
+    for i in range(args.reps + 2):
+        ctx.reset_stats()
+        w.fill_claims(1, kept, rows=n)
+        st = ctx.kernel_stats()["witness_claims"]
+        if i >= 2:
+            t_cp.append(st["ms"])
+    ctx.set_profile([])
+    line("compaction launches of one call (device time)", t_cp)
+    print("compaction: %d stated bytes per row (8 (W + 1) written by the pass, 8 (W + 1) read, 8 W written; every row kept), %.1f MB in all; the "
+          "launches move the last two, %.1f MB, in %.3f ms = %.0f GB/s" % (stated // n, stated / 1e6, (stated - 8 * (W + 1) * n) / 1e6, m(t_cp),
+                                                                          (stated - 8 * (W + 1) * n) / m(t_cp) / 1e6))
+    assert np.array_equal(state["host"].claims()[1], packed[1]) and np.array_equal(w.claims()[1], packed[1])
+    state.clear()  # witnesses go before their system
+    del w
+
+
+if args.claims:
+    claims_leg()
+    sys.exit(0)
 if args.gather:
     gather_leg()
     sys.exit(0)
