@@ -266,6 +266,13 @@ extern "C" {
                              producer_stream: *mut c_void, summary: *mut u64) -> i32;
     pub fn msbb_fill_program_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
     pub fn msbb_fill_scan_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
+    /// mode: 0 = MS_CLAIMS_REPLACE, 1 = MS_CLAIMS_APPEND; summary: 4 words
+    pub fn msbb_witness_claims_fill(w: *mut msbb_witness, circuit: usize, program: *const u8, program_len: usize, rows: usize,
+                                    inputs: *const ms_dev_matrix, producer_stream: *mut c_void, mode: u32, summary: *mut u64) -> i32;
+    pub fn msbb_claims_program_info(program: *const u8, program_len: usize, out4: *mut u64) -> i32;
+    /// canonical u32 values, read back from the device copy
+    pub fn msbb_witness_claims(w: *mut msbb_witness, offsets_out: *mut u64, cap_offsets: usize, data_out: *mut u32, cap_data: usize,
+                               n_claims: *mut usize, n_elems: *mut usize) -> i32;
     /// what: 0 = MS_SORT_PERM, 1 = MS_SORT_RANK; summary: 4 words
     pub fn msbb_witness_argsort(w: *mut msbb_witness, circuit: usize, key_columns: *const u32, n_keys: usize, dst_column: u32, what: u32,
                                 summary: *mut u64) -> i32;

@@ -508,7 +508,7 @@ int32_t ms_fill_peer_info(const uint8_t* program, size_t program_len, uint64_t* 
 /* ---- CLAIM PROGRAMS: the claims of a witness built on the device from its traces. Claims can otherwise only be given when a
  * witness is created, before any column has been filled; for most systems they are a function of filled columns (the bench
  * workload's [1, x, y, z] per addition). With this call the route pairs -> fill -> claims -> multiplicities -> check -> prove
- * leaves HBM only for the proof bytes. Goldilocks / BLAKE3 configuration.
+ * leaves HBM only for the proof bytes. Goldilocks / BLAKE3 configuration (the other's: msbb_witness_claims_fill, mstark_bb.h).
  *   Definition. A claim program has W expressions, the elements of one claim (1 <= W <= 2^16), and optionally a `keep`
  * expression. They are written in the algebra of fill programs: constants, main / preprocessed / input variables at offset 0
  * or 1, row, add, sub, mul, neg, bits, inv0, lt, xor, and, and indexed reads (`at`) of the three sources. A claim program

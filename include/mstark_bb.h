@@ -221,8 +221,8 @@ int32_t msbb_witness_derive_multiplicities(msbb_witness* w, const ms_mult_target
  * mul root, init] with strictly ascending step indices and init < p. Nodes that no step reaches are not subject to the
  * offset-1 rule in this format. Each call goes on refusing BOTH magics of the other field as a wrong magic.
  * msbb_witness_fill also refuses the third format of include/mstark.h ("PEER READS", magic "\0MFILL03") by its magic: this
- * configuration has no peer reads yet. Claim programs (ms_witness_claims_fill, "CLAIM PROGRAMS" there) are Goldilocks alone so
- * far as well: claims here are Montgomery words on the device and canonical vectors on the host.
+ * configuration has no peer reads yet. A claim program ("\0MCLAIB1", msbb_witness_claims_fill below) is refused as a wrong
+ * magic too: it is no fill program.
  *   Not part of this: accumulators over the degree-4 extension (four coupled columns that follow the previous row together,
  * as the running sum of a lookup argument over the challenge field) - a scan step is one base-field column.
  *   Execution: the groups in order on the context's stream - an ordinary group as above, a scan group as a coefficient pass
@@ -251,6 +251,59 @@ int32_t msbb_fill_program_info(const uint8_t* program, size_t program_len, uint6
 /* Host code, no device: the same checks, and out4 = [scan steps, launches of the fill kernel (one per group of ordinary steps,
  * one coefficient pass per scan), scans in the additive form, T = rows per scan tile]. Texts start "msbb_fill_scan_info: ". */
 int32_t msbb_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
+
+/* ---- Claim programs: ms_witness_claims_fill (include/mstark.h, "CLAIM PROGRAMS") for this configuration, its definition read
+ * over p = 2^31 - 2^27 + 1, with the same notions: W element expressions (1 <= W <= 2^16) and an optional keep, exactly one claim
+ * per kept row r < rows <= n in ascending row order, MS_CLAIMS_REPLACE / MS_CLAIMS_APPEND, the same summary words, the same
+ * refused nodes (peer sources, publics, selectors, stage-2 variables), no scan steps, neither the offset-1 rule nor the group
+ * rule, the next row of row n - 1 being row 0, an input row from the input height on reading 0 and an index from the source's
+ * height on reading 0 without a load. With it the route of the other configuration runs here too and leaves HBM only for the
+ * proof bytes: msbb_witness_create_device (zero traces, no claims), msbb_witness_fill, msbb_witness_claims_fill,
+ * msbb_witness_derive_multiplicities, msbb_witness_check, msbb_witness_lookup_balance, msbb_prove. What differs from the
+ * Goldilocks call:
+ *   The system comes from the witness, as for msbb_witness_fill.
+ *   Blob: the same layout - seven header words (magic, main_width, pre_width, n_inputs, n_nodes, W, keep root or all ones), the
+ * nodes, the W element roots - under a magic of its own, 0x314249414C434D00 ("\0MCLAIB1"): the blob carries no other mark of its
+ * field and its constants were folded modulo it (frontend.compile_claims under frontend.field(BABYBEAR)). Each configuration's
+ * calls refuse the other's claim magic, and the other's fill magics, as a wrong magic; "\0MFILB01" / "\0MFILB02" are named as "a
+ * fill program, not a claim program".
+ *   Values: as in msbb_witness_fill - operands are the canonical integers in [0, p), bits needs lo + length <= 32, xor folds
+ * once, a constant >= p is refused, row is r.
+ *   inputs: elem_bytes 1, 2 or 4 (8-byte elements are refused); a 4-byte element >= p is refused, naming the first offender in
+ * row-major order.
+ *   Storage: on the device the claim list is row-major Montgomery words (claim k of a call is W consecutive words) with u64
+ * offsets, what msbb_prove and the level-2 calls read; on the host the witness keeps the canonical vectors the transcript
+ * absorbs. Both are replaced together. msbb_witness_claims shows canonical values. The keep flag is compared as the stored
+ * word: a stored cell is the Montgomery word in [0, p) of a canonical value, which is 0 exactly when the value is 0, so the
+ * kept rows are those of the definition. In append mode the new elements start wherever the old ones end; nothing assumes more
+ * than 4-byte alignment.
+ *   No held lookup values, no sliced and no remote witnesses exist in this configuration, so their refusals do not either.
+ *   Execution: the kernel of msbb_witness_fill (4-byte slots: 256 lanes up to 64 live slots, 128 up to 128, 64 up to 256, else a
+ * global scratch walked in row batches) with a row-major output of rows x (W + keep) words - the traces are column-major, so
+ * with W > 1 a wave's stores are W words apart. Without keep it writes straight into the new claim data; with keep into a
+ * temporary that the three launches of the Goldilocks call compact over tiles of 1024 rows, on 4-byte words. Bytes per row:
+ * 4 (W + 1) written by the pass, the flag read twice, and 4 W read and 4 W written per kept row; 16 bytes per tile.
+ *   The guarantee is that of the Goldilocks call: the new offset and data arrays, device and host, are built beside the
+ * witness's own and change places with them last, so MS_ERR at any point - a refusal, an allocation failure, a non-canonical
+ * input - leaves claims and traces byte-identical and the context usable. Traces are never written.
+ *   Host waits: at most two - the inputs' offender word and the kept total in one read-back (not needed without inputs and
+ * without keep), then the host copy: one read-back of the new elements, converted to canonical on the host.
+ *   MS_ERR (texts start "msbb_witness_claims_fill: "): a null w, program or summary; a host-resident witness; a witness of
+ * another system; mode neither 0 nor 1; a circuit out of range, inactive or without a trace on this device; a blob that
+ * msbb_claims_program_info refuses; widths other than the circuit's; a preprocessed trace that is not on the device at this
+ * height; rows > n; the input refusals of msbb_witness_fill; a total of 2^60 elements or more. */
+int32_t msbb_witness_claims_fill(msbb_witness* w, size_t circuit, const uint8_t* program, size_t program_len, size_t rows,
+                                 const ms_dev_matrix* inputs /* nullable with n_inputs 0 */, void* producer_stream /* hipStream_t, nullable */,
+                                 uint32_t mode, uint64_t summary[4]);
+/* Host code, no device: checks a claim program as msbb_witness_claims_fill does (everything that needs no witness): out4 =
+ * [instructions per row, live slots, lanes per workgroup of the LDS form (0: global scratch), W | has_keep << 32]; the refusals
+ * of ms_claims_program_info over this field's magics, modulus and value width. Texts start "msbb_claims_program_info: ". */
+int32_t msbb_claims_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]);
+/* Diagnostic, as ms_witness_claims: the claims read back from the DEVICE copy and shown as canonical values. *n_claims and
+ * *n_elems are always set; offsets_out receives *n_claims + 1 words, data_out *n_elems. MS_ERR_BUFFER when a capacity is too
+ * small; nothing is written then. A host-resident witness: MS_ERR. */
+int32_t msbb_witness_claims(msbb_witness* w, uint64_t* offsets_out, size_t cap_offsets, uint32_t* data_out, size_t cap_data, size_t* n_claims,
+                            size_t* n_elems);
 
 /* ---- The sorting permutation of a circuit's rows, made on the device: ms_witness_argsort (include/mstark.h, "The sorting
  * permutation of a circuit's rows") for this configuration, its definition read over p = 2^31 - 2^27 + 1: row i comes before

@@ -25,7 +25,8 @@ def exported_symbols():
             "msbb_system_preprocessed_mmcs", "msbb_witness_commit_stage1", "msbb_witness_claims_accumulator", "msbb_stage2_build",
             "msbb_pcs_commit_traces", "msbb_quotient", "msbb_pcs_commit_ldes", "msbb_pcs_open", "msbb_witness_check", "msbb_system_check_info",
             "msbb_witness_lookup_balance", "msbb_system_multiplicity_slot", "msbb_witness_derive_multiplicities", "msbb_witness_trace",
-            "msbb_witness_fill", "msbb_fill_program_info", "msbb_fill_scan_info", "msbb_witness_argsort", "msbb_sort_info"]
+            "msbb_witness_fill", "msbb_fill_program_info", "msbb_fill_scan_info", "msbb_witness_argsort", "msbb_sort_info",
+            "msbb_witness_claims_fill", "msbb_claims_program_info", "msbb_witness_claims"]
 
 
 import sys
@@ -97,6 +98,22 @@ def compile_fill(main_width, preprocessed_width, n_inputs, steps):
         return frontend.compile_fill(main_width, preprocessed_width, n_inputs, steps, scans=True)
 
 
+def compile_claims(main_width, preprocessed_width, n_inputs, elements, keep=None):
+    """frontend.compile_claims over this field: the program is authored under frontend.field(BABYBEAR) - build the expressions
+    under it too where they hold constants, which are folded modulo the field in force - and comes out under the magic
+    "\\0MCLAIB1". -> frontend.ClaimProgram"""
+    with frontend.field(frontend.BABYBEAR):
+        return frontend.compile_claims(main_width, preprocessed_width, n_inputs, elements, keep=keep)
+
+
+def claims_program_info(program):
+    """msbb_claims_program_info (host only): checks a claim program (babybear.compile_claims, or its blob) and tells how
+    Witness.fill_claims would run it -> {"instructions", "slots", "lds_lanes" (0: global scratch), "width", "has_keep"}"""
+    a, o = _pkg()._program_bytes(program), np.zeros(4, dtype=np.uint64)
+    _check(_lib().msbb_claims_program_info(a.ctypes.data_as(u8p), C.c_size_t(a.size), o.ctypes.data_as(u64p)))
+    return {"instructions": int(o[0]), "slots": int(o[1]), "lds_lanes": int(o[2]), "width": int(o[3]) & 0xFFFFFFFF, "has_keep": bool(int(o[3]) >> 32)}
+
+
 def sort_info():
     """msbb_sort_info (host only) -> (T = rows per tile, bits per digit, R = per-tile counts per round of the offsets step,
     largest number of key columns) of Witness.argsort"""
@@ -139,6 +156,48 @@ class Witness:
         _check(_lib().msbb_witness_fill(self.h, C.c_size_t(circuit), a.ctypes.data_as(u8p), C.c_size_t(a.size),
                                         C.byref(mat) if mat is not None else None, pkg._producer_stream(stream, seen), summary.ctypes.data_as(u64p)))
         return pkg.FillReport(*(int(x) for x in summary))
+
+    def fill_claims(self, circuit, program, rows=None, inputs=None, append=False, stream=None):
+        """msbb_witness_claims_fill: the claims that `program` (babybear.compile_claims, or its blob) emits for rows [0, rows) of
+        `circuit` (default: its whole height), one per row the program keeps, built on the device from the traces; they replace the
+        witness's claims or, with append=True, follow them. inputs (1, 2 or 4-byte elements) and stream as for fill. The traces
+        are not touched. Pipeline order: fill, fill_claims, derive_multiplicities, check, prove. -> the package's ClaimsReport"""
+        pkg = _pkg()
+        a = pkg._program_bytes(program)
+        mat, seen = None, None
+        if inputs is not None:
+            ptr, shape, strides, item, is_torch = pkg._device_array(inputs, "fill_claims inputs")
+            if len(shape) != 2:
+                raise pkg.MstarkError("fill_claims inputs: expected a 2-D matrix, got %d dimension(s)" % len(shape))
+            (h, w), (rs, cs) = shape, strides
+            want = int(a[24:32].view("<u8")[0]) if a.size >= 56 else w  # the blob's n_inputs word (a shorter blob is refused below)
+            if w != want:
+                raise pkg.MstarkError("fill_claims inputs: width %d, the program reads %d input columns" % (w, want))
+            seen = inputs if is_torch else None
+            mat = pkg.DevMatrix(ptr or None, h, item, rs if h > 1 else max(w, 1), cs if w > 1 else 1)
+        if rows is None:
+            need = C.c_size_t()
+            rc = _lib().msbb_witness_trace(self.h, C.c_size_t(circuit), None, C.c_size_t(0), C.byref(need))
+            if rc != -3:
+                _check(rc)
+            rows = need.value // max(self.system.circuit_info(circuit)["main_width"], 1)
+        summary = np.zeros(4, dtype=np.uint64)
+        _check(_lib().msbb_witness_claims_fill(self.h, C.c_size_t(circuit), a.ctypes.data_as(u8p), C.c_size_t(a.size), C.c_size_t(rows),
+                                               C.byref(mat) if mat is not None else None, pkg._producer_stream(stream, seen),
+                                               C.c_uint32(pkg.CLAIMS_APPEND if append else pkg.CLAIMS_REPLACE), summary.ctypes.data_as(u64p)))
+        return pkg.ClaimsReport(*(int(x) for x in summary))
+
+    def claims(self):
+        """the claims of a device-resident witness read back from the device (msbb_witness_claims) -> (offsets: n_claims + 1
+        uint64, data: uint32, canonical); claim i is data[offsets[i]:offsets[i + 1]]"""
+        n, e = C.c_size_t(), C.c_size_t()
+        rc = _lib().msbb_witness_claims(self.h, None, C.c_size_t(0), None, C.c_size_t(0), C.byref(n), C.byref(e))
+        if rc != -3:  # (MS_ERR_BUFFER: the counts)
+            _check(rc)
+        offs, data = np.zeros(n.value + 1, dtype=np.uint64), np.zeros(e.value, dtype=np.uint32)
+        _check(_lib().msbb_witness_claims(self.h, offs.ctypes.data_as(u64p), C.c_size_t(offs.size), _p32(data), C.c_size_t(data.size), C.byref(n),
+                                          C.byref(e)))
+        return offs, data
 
     def check(self, beta=None, gamma=None, names=None, origins=None):
         """msbb_witness_check: every user constraint root of every active circuit on the trace domain, and the lookup balance

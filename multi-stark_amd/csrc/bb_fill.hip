@@ -20,8 +20,11 @@
 //     from the lane before it (lane 0 of a wave loads it itself). The dst column of a column-major trace is contiguous: the four
 //     cells are one 16-byte store under the same two conditions - with ld below 4 (heights 1 and 2) or a dst column that starts
 //     off a 16-byte boundary, 4-byte stores. A tile's aggregate lies split: a in aggs[t], b in aggs[n_tiles + t].
+//
+// CLAIM PROGRAMS (msbb_witness_claims_fill, below the fill): the same interpreter over the first rows of a trace with a row-major
+// output, the witness's new claims; the driver is claims_fill.h, shared with Goldilocks.
 #include "bb_host.h"
-#include "fill_dev.h"
+#include "claims_fill.h"
 
 namespace msbb {
 
@@ -156,6 +159,95 @@ void fill_scan_info(const uint8_t* program, size_t program_len, u64 out4[4]) { f
 void witness_fill(BSystem& sys, BWitness& wit, size_t ci, const uint8_t* program, size_t program_len, const ms_dev_matrix* inputs,
                   void* producer_stream, u64 summary[4]) {
   fl_witness_fill<BbFill>(sys, wit, ci, program, program_len, inputs, producer_stream, summary);
+}
+
+// ---- msbb_witness_claims_fill: the claims of a witness from its traces (include/mstark_bb.h; the definition is "CLAIM PROGRAMS"
+// of include/mstark.h). The driver is cl_witness_claims_fill of claims_fill.h; what BabyBear decides:
+//   - the traces are column-major and the claim list is ROW-major (claim k is W consecutive words), so the pass is
+//     fill_k<BbClaimFill, *>: BbFill with a View of its own whose store writes d_out[row * out_w + col]. Reads are BbFill's. With
+//     W > 1 the 4-byte stores of a wave are W words apart, not contiguous (DESIGN.md has the measured cost);
+//   - the words are Montgomery words in [0, p) on the device - what the pass stores (F::stored) is what d_claim_data holds - and
+//     a keep flag is compared as the stored word: the Montgomery word of v is 0 exactly when v is 0;
+//   - the compaction is claims_dev.h instantiated for u32. Bytes per row with S = 4: the pass writes 4 (W + 1), the count launch
+//     reads 4 (the flag; one 32-byte sector where W + 1 >= 8), the scatter reads 4 again and 4 W per kept row and writes 4 W per
+//     kept row; counts and offsets stay 16 bytes per tile;
+//   - the host copy, BWitness::claims, is one canonical vector per claim (the transcript absorbs them): the new elements are
+//     read back once, converted on the host and cut into vectors of W beside the witness's list;
+//   - no claims_partial and no has_remote: neither form of witness exists in this configuration.
+namespace {
+
+struct BbClaimFill : BbFill {
+  struct View : BbFill::View {
+    uint32_t out_w;  // d_out is rows x out_w row-major here; out_ld is not used
+    __device__ __forceinline__ void store(size_t row, u32 col, u32 v) const { d_out[row * out_w + col] = v; }
+    void to_tmp(u32* out, uint32_t cols) { d_out = out, out_w = cols; }
+  };
+};
+
+struct BbClaims {
+  using Fill = BbClaimFill;
+  static constexpr const char* call = "msbb_witness_claims_fill";
+  static void fail(const std::string& what) { throw std::runtime_error(std::string(call) + ": " + what); }
+  static void accept(BSystem& sys, BWitness& wit) {
+    const size_t C = sys.circuits.size();
+    if (wit.sys != &sys || wit.heights.size() != C || wit.traces.size() != C) fail("the witness does not belong to this system");
+    if (wit.host_resident) fail("takes a device-resident witness (msbb_witness_create, msbb_witness_create_device)");
+  }
+  static BbClaimFill::View trace(BSystem& sys, BWitness& wit, size_t ci) {
+    if (ci >= sys.circuits.size()) fail("circuit " + std::to_string(ci) + " is out of range");
+    const size_t n = wit.heights[ci];
+    if (!n) fail("circuit " + std::to_string(ci) + " is inactive (height 0)");
+    const BCircuit& c = sys.circuits[ci];
+    const BMat& tr = wit.traces[ci];
+    if (!tr.buf.p || tr.h != n || tr.w != c.main_width || tr.ld < n) fail("the circuit has no trace on this device");
+    const bool pre = c.pre_width && n == c.pre_height && c.pre.buf.p && c.pre.h == n && c.pre.w == c.pre_width && c.pre.ld >= n;
+    BbClaimFill::View v{};
+    v.d_main = tr.buf.p, v.ld = tr.ld;
+    v.d_pre = pre ? c.pre.buf.p : nullptr, v.pre_ld = pre ? c.pre.ld : 0;
+    v.n = n;
+    return v;
+  }
+  static size_t n_claims(const BWitness& wit) { return wit.claims.size(); }
+  static size_t n_elems(const BWitness& wit) {
+    size_t e = 0;
+    for (auto& cl : wit.claims) e += cl.size();
+    return e;
+  }
+  static const u64* d_offs(const BWitness& wit) { return wit.d_claim_offs.p; }
+  static const u32* d_data(const BWitness& wit) { return wit.d_claim_data.p; }
+  struct Host {
+    const BWitness& wit;
+    std::vector<std::vector<u32>> claims;  // canonical: the claims that stay, then the new ones
+    std::vector<u32> flat;                 // the new elements as they lie on the device
+    size_t n_base, W;
+    Host(const BWitness& wit, size_t n_base, size_t, size_t kept, size_t W) : wit(wit), flat(kept * W), n_base(n_base), W(W) {
+      claims.reserve(n_base + kept);
+    }
+    void read(Ctx& ctx, const u64*, const u32* d_new_data) {  // (the claims that stay are copied while the device works)
+      claims.assign(wit.claims.begin(), wit.claims.begin() + n_base);
+      ctx.d2h(flat.data(), d_new_data, flat.size() * 4);
+      for (size_t k = 0; k * W < flat.size(); k++) {
+        claims.emplace_back(W);
+        for (size_t e = 0; e < W; e++) claims.back()[e] = bb_from_monty(flat[k * W + e]);
+      }
+    }
+    void publish(BWitness& wit, DBuf<u64>&& d_new_offs, DBuf<u32>&& d_new_data) {
+      wit.claims.swap(claims);
+      wit.d_claim_offs = std::move(d_new_offs);
+      wit.d_claim_data = std::move(d_new_data);
+    }
+  };
+};
+
+}  // namespace
+
+void claims_program_info(const uint8_t* program, size_t program_len, u64 out4[4]) {
+  cl_program_info<BbClaims>(program, program_len, "msbb_claims_program_info", out4);
+}
+
+void witness_claims_fill(BSystem& sys, BWitness& wit, size_t ci, const uint8_t* program, size_t program_len, size_t rows, const ms_dev_matrix* inputs,
+                         void* producer_stream, uint32_t mode, u64 summary[4]) {
+  cl_witness_claims_fill<BbClaims>(sys, wit, ci, program, program_len, rows, inputs, producer_stream, mode, summary);
 }
 
 }  // namespace msbb

@@ -201,6 +201,12 @@ void witness_fill(BSystem& sys, BWitness& wit, size_t circuit, const uint8_t* pr
 void fill_program_info(const uint8_t* program, size_t program_len, u64 out4[4]);  // host only: [instructions, slots, LDS lanes, assigned columns]
 // msbb_fill_scan_info: host only - [scan steps, launches of the fill kernel, scans in the additive form, rows per scan tile]
 void fill_scan_info(const uint8_t* program, size_t program_len, u64 out4[4]);
+// msbb_witness_claims_fill (bb_fill.hip): the claims a claim program emits for the first `rows` rows of circuit `ci`, in place of the
+// witness's claims or behind them; the traces are not written. At most two host waits; any error leaves the witness as it was
+void witness_claims_fill(BSystem& sys, BWitness& wit, size_t ci, const uint8_t* program, size_t program_len, size_t rows, const ms_dev_matrix* inputs,
+                         void* producer_stream, uint32_t mode, u64 summary[4]);
+// msbb_claims_program_info: host only - [instructions, live slots, lanes of the LDS form (0: global scratch), W | has_keep << 32]
+void claims_program_info(const uint8_t* program, size_t program_len, u64 out4[4]);
 // msbb_witness_argsort (bb_argsort.hip): the stable sorting permutation of circuit `ci`'s rows under the key columns, cells compared
 // as canonical values (or its inverse, what = 1), written into main column dst as Montgomery words. One host wait: the digit histograms
 void witness_argsort(BSystem& sys, BWitness& wit, size_t ci, const uint32_t* key_columns, size_t n_keys, uint32_t dst, uint32_t what,

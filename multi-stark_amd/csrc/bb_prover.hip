@@ -1591,6 +1591,49 @@ int32_t msbb_fill_scan_info(const uint8_t* program, size_t program_len, uint64_t
   return MS_OK;
   BB_CATCH
 }
+int32_t msbb_witness_claims_fill(msbb_witness* w, size_t circuit, const uint8_t* program, size_t program_len, size_t rows, const ms_dev_matrix* inputs,
+                                 void* producer_stream, uint32_t mode, uint64_t summary[4]) {
+  BB_TRY
+  if (!w || !program || !summary) throw std::runtime_error("msbb_witness_claims_fill: null argument");
+  BWitness& wit = *w->w;
+  BSystem& sys = *wit.sys;
+  HIP_CHECK(hipSetDevice(sys.ctx->device));
+  witness_claims_fill(sys, wit, circuit, program, program_len, rows, inputs, producer_stream, mode, summary);
+  return MS_OK;
+  BB_CATCH
+}
+int32_t msbb_claims_program_info(const uint8_t* program, size_t program_len, uint64_t out4[4]) {
+  BB_TRY
+  if (!program || !out4) throw std::runtime_error("msbb_claims_program_info: null argument");
+  claims_program_info(program, program_len, out4);
+  return MS_OK;
+  BB_CATCH
+}
+int32_t msbb_witness_claims(msbb_witness* w, uint64_t* offsets_out, size_t cap_offsets, uint32_t* data_out, size_t cap_data, size_t* n_claims,
+                            size_t* n_elems) {
+  BB_TRY
+  if (!w || !n_claims || !n_elems) throw std::runtime_error("msbb_witness_claims: null argument");
+  BWitness& wit = *w->w;
+  if (wit.host_resident) throw std::runtime_error("msbb_witness_claims: a host-resident witness keeps its claims on the host between proofs");
+  size_t elems = 0;
+  for (auto& cl : wit.claims) elems += cl.size();
+  *n_claims = wit.claims.size();
+  *n_elems = elems;
+  if (*n_claims + 1 > cap_offsets || elems > cap_data) return MS_ERR_BUFFER;
+  if (!offsets_out || (elems && !data_out)) throw std::runtime_error("msbb_witness_claims: null output");
+  if (!*n_claims) {  // (a witness created without claims has no device arrays)
+    offsets_out[0] = 0;
+    return MS_OK;
+  }
+  Ctx& ctx = *wit.sys->ctx;
+  HIP_CHECK(hipSetDevice(ctx.device));
+  if (!wit.d_claim_offs.p || (elems && !wit.d_claim_data.p)) throw std::runtime_error("msbb_witness_claims: the witness has no claims on this device");
+  ctx.d2h_queue(offsets_out, wit.d_claim_offs.p, (*n_claims + 1) * 8);
+  ctx.d2h(data_out, wit.d_claim_data.p, elems * 4);
+  for (size_t i = 0; i < elems; i++) data_out[i] = bb_from_monty(data_out[i]);  // the device holds Montgomery words
+  return MS_OK;
+  BB_CATCH
+}
 int32_t msbb_witness_argsort(msbb_witness* w, size_t circuit, const uint32_t* key_columns, size_t n_keys, uint32_t dst_column, uint32_t what,
                              uint64_t summary[4]) {
   BB_TRY

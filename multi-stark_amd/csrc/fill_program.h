@@ -28,7 +28,7 @@
 // the column. The call never writes a peer, so such a node has deps = 0, keeps one instance per pass and falls under no group
 // rule; the source travels in the immediates as it stands. Apart from that the format is the second: groups, 0 scans allowed.
 //
-// CLAIM PROGRAMS (ms_witness_claims_fill; magic "\0MCLAIM1", a format of its own): W element roots and an optional keep root over
+// CLAIM PROGRAMS (ms_witness_claims_fill, msbb_witness_claims_fill; magic "\0MCLAIM1", over BabyBear "\0MCLAIB1", a format of its own): W element roots and an optional keep root over
 // the same nodes, no steps. claims_compile reads and checks the nodes with the functions fill_compile uses (fill_read_nodes,
 // fill_check_nodes: one text and one order of refusals), without the rules of assigned columns - nothing is assigned, so every
 // main column may be read at the next row or at a computed row - and with peer sources refused; it linearises ONE pass with
@@ -57,7 +57,8 @@ struct FillField {
 };
 constexpr FillField FILL_GOLDILOCKS{0x31304C4C49464D00ull, 0xFFFFFFFF00000001ull, 64, 0x32304C4C49464D00ull, 0x33304C4C49464D00ull,
                                     0x314D49414C434D00ull};                                                 // "\0MFILL01", "\0MFILL02", "\0MFILL03", "\0MCLAIM1"
-constexpr FillField FILL_BABYBEAR{0x3130424C49464D00ull, 0x78000001ull, 32, 0x3230424C49464D00ull, 0, 0};  // "\0MFILB01", "\0MFILB02"
+constexpr FillField FILL_BABYBEAR{0x3130424C49464D00ull, 0x78000001ull, 32, 0x3230424C49464D00ull, 0,
+                                  0x314249414C434D00ull};                                                   // "\0MFILB01", "\0MFILB02", "\0MCLAIB1"
 
 constexpr uint32_t FL_NONE = ~0u;
 constexpr uint32_t FL_SRC_PRE = 0, FL_SRC_MAIN = 1, FL_SRC_INPUT = 3, FL_SRC_PEER = 4;  // source 4 + k: peer k of the program

@@ -33,16 +33,16 @@ FILL_MAGIC = 0x31304C4C49464D00  # "\0MFILL01"; over BabyBear "\0MFILB01": a fil
 FILL_BITS = 64  # bits(x, lo, length) needs lo + length <= the width of a value: 64, over BabyBear 32
 FILL_SCAN_MAGIC = 0x32304C4C49464D00  # "\0MFILL02": a program with scan steps; over BabyBear "\0MFILB02"
 FILL_PEER_MAGIC = 0x33304C4C49464D00  # "\0MFILL03": a program with peer reads (Goldilocks alone)
-CLAIM_MAGIC = 0x314D49414C434D00  # "\0MCLAIM1": a claim program (compile_claims, ms_witness_claims_fill; Goldilocks alone so far)
+CLAIM_MAGIC = 0x314D49414C434D00  # "\0MCLAIM1": a claim program (compile_claims, ms_witness_claims_fill); over BabyBear "\0MCLAIB1"
 CLAIM_MAX_WIDTH = 1 << 16
 SRC_PEER, FL_MAX_PEERS = 4, 8  # source byte 4 + k: peer record k of the program (include/mstark.h, "PEER READS")
 
 # The two StarkGenericConfig instantiations of the reference: GoldilocksBlake3Config (src/types.rs:24-29,199-223) and
 # the BabyBear / degree-4 extension / Poseidon2 test configuration (src/test_circuits/baby_bear_config.rs:28-38).
 GOLDILOCKS = dict(name="goldilocks", P=P, EXT_D=2, EXT_W=7, BLOB_MAGIC=0x31305359534D0000, FILL_MAGIC=0x31304C4C49464D00, FILL_BITS=64,
-                  FILL_SCAN_MAGIC=0x32304C4C49464D00)
+                  FILL_SCAN_MAGIC=0x32304C4C49464D00, CLAIM_MAGIC=0x314D49414C434D00)
 BABYBEAR = dict(name="babybear", P=(1 << 31) - (1 << 27) + 1, EXT_D=4, EXT_W=11, BLOB_MAGIC=0x31304259534D0000, FILL_MAGIC=0x3130424C49464D00,
-                FILL_BITS=32, FILL_SCAN_MAGIC=0x3230424C49464D00)
+                FILL_BITS=32, FILL_SCAN_MAGIC=0x3230424C49464D00, CLAIM_MAGIC=0x314249414C434D00)
 
 
 @contextlib.contextmanager
@@ -50,7 +50,7 @@ def field(cfg):
     """Author circuits / witnesses / blobs over another configuration's field: `with frontend.field(frontend.BABYBEAR):`.
     (The reference picks the field through the SC type parameter; this front-end keeps it in module state.)"""
     g = globals()
-    saved = {k: g[k] for k in ("P", "EXT_D", "EXT_W", "BLOB_MAGIC", "FILL_MAGIC", "FILL_BITS", "FILL_SCAN_MAGIC")}
+    saved = {k: g[k] for k in ("P", "EXT_D", "EXT_W", "BLOB_MAGIC", "FILL_MAGIC", "FILL_BITS", "FILL_SCAN_MAGIC", "CLAIM_MAGIC")}
     g.update({k: cfg[k] for k in saved})
     try:
         yield cfg
@@ -984,9 +984,8 @@ class ClaimProgram:
 
 def compile_claims(main_width, preprocessed_width, n_inputs, elements, keep=None):
     """elements: the W expressions of one claim, 1 <= W <= 2^16; keep: None (every row emits a claim) or an expression (the rows
-    where it is non-zero do). -> ClaimProgram"""
-    if FILL_MAGIC != GOLDILOCKS["FILL_MAGIC"]:
-        raise CompileError("ClaimProgramInThisField: claim programs: Goldilocks configuration only")
+    where it is non-zero do). The program belongs to the field in force (`field(BABYBEAR)`: the magic "\\0MCLAIB1", constants
+    folded modulo that p, bits up to 32). -> ClaimProgram"""
     spec = {"main_width": int(main_width), "preprocessed_width": int(preprocessed_width), "n_inputs": int(n_inputs), "peers": None, "claims": True}
     elements = list(elements)
     if not 1 <= len(elements) <= CLAIM_MAX_WIDTH:
@@ -1008,7 +1007,8 @@ def compile_claims(main_width, preprocessed_width, n_inputs, elements, keep=None
 
 def u32_add_claims_program():
     """The claims of the U32Add circuit (u32_add_system_inputs) from its filled trace, [1, x, y, z] per addition with the words
-    put together from their byte columns: call it with rows = the number of additions."""
+    put together from their byte columns: call it with rows = the number of additions. Under `field(BABYBEAR)` the words are
+    taken modulo p, as frontend.u32_add_bench_witness's claims are there."""
     def word(i):
         return sum((Expr.main(i + k) * Expr.const(256 ** k) for k in range(1, 4)), Expr.main(i))
 

@@ -51,6 +51,13 @@ moves the most it can); the whole device route, fill + fill_claims + derive_mult
 ms_witness_trace, numpy, and a new ms_witness_create_device from the traces in HBM with the claims given by the host; and the
 hand-written generator. The compaction's time is the difference of the two fill_claims lines, printed next to the bytes its
 layout states (8 (W + 1) written and read and 8 W written per kept row); it is no share of a peak.
+  python tools/witness_fill.py --claims --config babybear [--log-size 20] [--reps 9] [--width 4|49]
+the same call over BabyBear (msbb_witness_claims_fill): the route on the bench workload, checked against the host builder and the
+host-built witness's proof; then, in a lab circuit of 14 + W columns (W = 4: the bench claims, W = 49: as wide as the BLAKE3
+system's), the claims call without keep next to msbb_witness_fill assigning the same W expressions to W columns - one
+interpreter, row-major stores W words apart against contiguous column-major ones - and next to the read-back of the list alone;
+then the keep compaction at densities 1/64, 1/2 and 1 (profile class witness_claims) against its stated bytes. --width runs one
+width alone, so that a kernel trace of the run tells the two passes apart by name.
 Timing: wall time of each route (all return synchronised), alternating after two warm-up rounds; median, minimum and maximum are
 printed. No figure here is a share of peak."""
 import argparse
@@ -73,7 +80,8 @@ ap.add_argument("--reps", type=int, default=9)
 ap.add_argument("--scan", action="store_true", help="the scan-step leg (both configurations)")
 ap.add_argument("--gather", action="store_true", help="the indexed-read leg (both configurations)")
 ap.add_argument("--peers", action="store_true", help="the peer-read leg (Goldilocks)")
-ap.add_argument("--claims", action="store_true", help="ms_witness_claims_fill on the bench workload (Goldilocks)")
+ap.add_argument("--claims", action="store_true", help="ms_witness_claims_fill on the bench workload (--config babybear: msbb_witness_claims_fill)")
+ap.add_argument("--width", type=int, default=0, choices=[0, 4, 49], help="--claims --config babybear: one claim width alone (for a kernel trace)")
 ap.add_argument("--alone", action="store_true", help="ms_witness_fill of U32Add alone in the process (Goldilocks)")
 args = ap.parse_args()
 
@@ -576,8 +584,106 @@ def claims_leg():
     del w
 
 
+def claims_leg_bb():
+    """--claims --config babybear: msbb_witness_claims_fill. The route on the bench workload; the price of the row-major store,
+    the claims pass next to msbb_witness_fill evaluating the same expressions as steps into as many columns; the compaction."""
+    bb = pkg.babybear
+    E = fe.Expr
+    k = fe.poseidon2_constants()
+    bb.set_poseidon2(ctx, k)
+    xs, ys = fe.xorshift_pairs(n)
+    with fe.field(fe.BABYBEAR):
+        system = bb.System.new(ctx, fe.test_params(), fe.u32_add_system_inputs(), k)
+        traces, claims = fe._u32_add_traces(xs, ys, n)
+        packed = fe.pack_claims(claims)  # (a 2-D array: reduced mod p)
+        fill_prog, plain = fe.u32_add_halves_fill_program(n), fe.u32_add_claims_program()
+    print("claim program of the bench workload: %d nodes; %s" % (len(plain.nodes), bb.claims_program_info(plain)))
+    m16, s16 = np.uint64(0xFFFF), np.uint64(16)
+    halves = torch.from_numpy(np.stack([xs & m16, xs >> s16, ys & m16, ys >> s16], axis=1).astype(np.uint16).view(np.int16)).cuda()
+    w = system.witness_from_device([torch.zeros(t.shape, dtype=torch.int32, device="cuda") for t in traces], fe.pack_claims([]))
+    w.fill(1, fill_prog, halves)
+    rep = w.fill_claims(1, plain, rows=n)
+    offs, data = w.claims()
+    same = bool(np.array_equal(offs, packed[0])) and bool(np.array_equal(data, packed[1]))
+    dm = w.derive_multiplicities(TARGETS)
+    proof = system.prove_multiple_claims(w).to_bytes()
+    same_proof = proof == system.prove_multiple_claims(system.witness(traces, packed)).to_bytes()
+    print("u32add over BabyBear at 2^%d additions: %s; claims equal the host builder's mod p: %s; proof equals the host-built witness's: %s; "
+          "check().verdict: %d" % (args.log_size, rep, same, same_proof, w.check().verdict), flush=True)
+    assert same and same_proof and dm.ok
+    del w
+
+    # the lab system: per width W a circuit of 14 + W columns, the first 14 those of U32Add. The claim program's W elements read
+    # columns 0 .. 13; the fill program assigns the same W expressions to columns 14 .. 14 + W - 1: one interpreter, one program
+    # body, row-major 4-byte stores W words apart against column-major contiguous ones.
+    widths = [args.width] if args.width else [4, 49]
+    with fe.field(fe.BABYBEAR):
+        word = lambda i: sum((E.main(i + j) * E.const(256 ** j) for j in range(1, 4)), E.main(i))
+        elements = {4: [E.const(1), word(0), word(4), word(8)], 49: [E.main(j % 14) * (j + 2) + E.main_next((j + 5) % 14) for j in range(49)]}
+        ph = [E.main(0) * E.main(0) - E.main(0)]
+        lab = bb.System.new(ctx, fe.test_params(), [fe.CircuitInputs(14 + W, None, ph, [], []) for W in widths], k)
+        progs = {W: (fe.compile_claims(14 + W, 0, 0, elements[W]), fe.compile_fill(14 + W, 0, 0, [(14 + j, e) for j, e in enumerate(elements[W])]),
+                     fe.compile_claims(14 + W, 0, 0, elements[W], keep=E.main(13))) for W in widths}
+    t1 = torch.from_numpy(np.ascontiguousarray(traces[1]).astype(np.uint32).view(np.int32)).cuda()
+    lw = lab.witness_from_device([torch.cat([t1, torch.zeros((n, W), dtype=torch.int32, device="cuda")], dim=1) for W in widths], fe.pack_claims([]))
+    del t1
+    fns, names = [], []
+    for ci, W in enumerate(widths):
+        cl, fl, _ = progs[W]
+        print("W = %d: claim program %s; fill program %s" % (W, bb.claims_program_info(cl), bb.fill_program_info(fl)))
+        lw.fill(ci, fl)
+        lw.fill_claims(ci, cl, rows=n)
+        got = lw.claims()[1].reshape(n, W)
+        assert np.array_equal(got, lw.trace(ci)[:, 14:]), "the claims are the filled columns, row by row"
+        if W == 4:
+            assert np.array_equal(got.reshape(-1), packed[1])
+
+        def claims_call(ci=ci, cl=cl):
+            lw.fill_claims(ci, cl, rows=n)  # (returns synchronised: its last step is the host copy)
+
+        def fill_call(ci=ci, fl=fl):
+            lw.fill(ci, fl)
+            ctx.sync()
+
+        def copy_alone(ci=ci):
+            lw.claims()  # the read-back of the list and nothing else: what the host copy of the call costs at least
+
+        fns += [claims_call, fill_call, copy_alone]
+        names += ["W = %d: msbb_witness_claims_fill, no keep" % W, "W = %d: msbb_witness_fill, the same %d expressions" % (W, W),
+                  "W = %d: Witness.claims() alone (the list read back)" % W]
+    print("\n# babybear, 2^%d rows: the claims pass next to the fill, alternating (wall time; the claims call ends in its host copy)" % args.log_size)
+    for name, t in zip(names, timed(fns, args.reps)):
+        line(name, t)
+
+    # the compaction: its launches between two events (the profile class witness_claims), one call at a time, W = 4
+    if 4 in widths:
+        ci, (_, _, kept) = widths.index(4), progs[4]
+        S, W = 4, 4
+        print("\n# the keep compaction at W = 4: device time of its launches against the bytes the layout states")
+        ctx.set_profile(["witness_claims"])
+        for name, dens in (("1/64", 64), ("1/2", 2), ("1", 1)):
+            act = (torch.arange(n, device="cuda") % dens == 0).to(torch.int32)
+            tr = torch.from_numpy(lw.trace(ci).view(np.int32)).cuda()
+            tr[:, 13] = act
+            cw = lab.witness_from_device([tr if c == ci else None for c in range(len(widths))], fe.pack_claims([]))
+            n_kept = int(act.sum().item())
+            t_cp = []
+            for i in range(args.reps + 2):
+                ctx.reset_stats()
+                assert cw.fill_claims(ci, kept, rows=n).claims == n_kept
+                if i >= 2:
+                    t_cp.append(ctx.kernel_stats()["witness_claims"]["ms"])
+            moved = 2 * S * n + 2 * S * W * n_kept  # the flag read by the count and by the scatter; each kept row read and written
+            line("density %s: compaction launches of one call" % name, t_cp)
+            print("    stated bytes: %d x 2 x %d (flags) + %d x 2 x %d (kept rows) = %.1f MB -> %.0f GB/s (no share of a peak: the flag reads "
+                  "touch one 32-byte sector per row)" % (n, S, n_kept, S * W, moved / 1e6, moved / statistics.median(t_cp) / 1e6), flush=True)
+            del cw
+        ctx.set_profile([])
+    del lw
+
+
 if args.claims:
-    claims_leg()
+    claims_leg_bb() if args.config == "babybear" else claims_leg()
     sys.exit(0)
 if args.gather:
     gather_leg()
